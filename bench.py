@@ -11,7 +11,8 @@ rank 0 and an on-device un-shard assemble the frame).
 Default workload = BASELINE config 3: 3840x2160, 3 reflection bounces, soft
 shadows, 4x supersampling, 1 MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..5] [--full]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) runs the same
@@ -27,7 +28,12 @@ Timing: barrier + device synchronise, t0, the K steps, each rank's streams drain
 + device synchronise, t1, barrier; `value` uses the max over ranks of t1 - t0 (the
 host barrier's own round trip is outside the interval, the slowest rank's end is in).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+A plain run sets up, spins up and warms up, times the K steps, writes the last
+step's frame under --dump-outputs DIR when given (dump_outputs), and prints the
+headline line: metric, value, ms_per_step, config.  --full adds, after the timed
+steps and outside `value`, every other measurement and check below.
+
+Rank 0 prints ONE JSON line.  Extra objects (--full):
   roofline        : FP32-VALU issue roofline of the dominant kernel (k_sample /
                     k_pixel): achieved = SQ_INSTS_VALU per launch (committed
                     rocprofv3 PMC pass over the same sweep frames, profiles/) x 64
@@ -341,6 +347,34 @@ def run_mode(gpus: int, launched: bool, ws: int, single_process: bool):
     return "single_gpu", None
 
 
+DUMP_MAX_PIXELS = 1 << 21  # x 4 channels x 4 B (+ 8 B per pixel index) = 48 MiB per dump
+
+
+def dump_outputs(path: str, frame: np.ndarray) -> dict:
+    """--dump-outputs DIR: the RGBA8 frame the last timed step rendered (what rm_read_rgba8
+    hands a caller: top row first, for N > 1 the frame rank 0 assembled), as float32 values
+    0..255 in DIR/frame_rgba8.npy.  A frame of at most DUMP_MAX_PIXELS pixels is written
+    whole, [H, W, 4]; of a larger one (the 4K and 8K configurations) a fixed sample of
+    DUMP_MAX_PIXELS pixels, [n, 4], drawn without replacement by numpy's default_rng(0)
+    and sorted, with their flat indices y * W + x in DIR/frame_rgba8_pixels.npy (float64,
+    exact below 2^53).  The sweep frames, and so the frame of the last step, depend on
+    --config, --steps and --scene alone: two builds run with the same arguments write
+    arrays that compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    h, w = frame.shape[:2]
+    info = {"dir": path, "frame_rgba8": {"dtype": "float32", "height": h, "width": w}}
+    if h * w <= DUMP_MAX_PIXELS:
+        out = frame.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_MAX_PIXELS, replace=False))
+        out = frame.reshape(h * w, -1)[idx].astype(np.float32)
+        np.save(os.path.join(path, "frame_rgba8_pixels.npy"), idx.astype(np.float64))
+        info["frame_rgba8"]["sampled_pixels"] = int(idx.size)
+    np.save(os.path.join(path, "frame_rgba8.npy"), out)
+    info["frame_rgba8"]["shape"] = list(out.shape)
+    return info
+
+
 def dist_env():
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -395,13 +429,27 @@ def main() -> int:
                     help="before the warmup steps, render sweep frames (untimed) for this long so "
                          "the GPU reaches its sustained clocks: with the 5-step warmup alone the "
                          "first timed frames run ~6%% slower (tools/probe_ramp.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the "
+                         "headline figure: the roofline and the algorithmic rate (a re-render with "
+                         "HIP events, an exact work-counter pass), the CPU baseline and the oracle "
+                         "parity, and for N > 1 the per-phase times, RCCL's own report and the "
+                         "assembled frame against a single-GPU render")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the frame the last timed step rendered to "
+                         "DIR/frame_rgba8.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline and its parity sample")
     ap.add_argument("--cpu-row-stride", type=int, default=0,
                     help="cpu_baseline renders every k-th row of one frame (0: the whole "
                          "frame for every BASELINE config)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = nproc, capped at the CPUs this process may run on")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print(f"bench.py: --steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})",
+              file=sys.stderr)
+        return 2
 
     # stdout carries exactly the one JSON line: library banners written to fd 1
     # (gloo's connection notice, RCCL's version block) go to stderr until then
@@ -594,9 +642,10 @@ def main() -> int:
     for i in range(0, len(frames_timed), batch):
         key = tuple(frames_timed[i:i + batch])
         barr.setdefault(key, [uniforms(f) for f in key])
-    for rj in rs:
-        rj.enable_timing(nfl == 1)
-        rj.kernel_time_ms(reset=True)
+    if args.full:
+        for rj in rs:
+            rj.enable_timing(nfl == 1)
+            rj.kernel_time_ms(reset=True)
     barrier()
     t0 = time.perf_counter()
     issue(frames_timed)
@@ -610,6 +659,84 @@ def main() -> int:
     sync_devices()
     t1 = time.perf_counter()
     barrier()
+    elapsed = t1 - t0
+    if dist_on:
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    frames = args.steps
+    value = frames * W * H / elapsed / 1e6  # whole-job Mpixels/s
+    batched = batch > 1 and not use_graph
+    kname = "k_sample" if cfg["aa"] else "k_pixel"
+    if scene is not None:
+        kname = "k_table_sample" if cfg["aa"] else "k_table_pixel"
+    if batched:
+        kname += "_frames"  # the batched kernels (grid.z = frame); PMC values per frame
+
+    def headline() -> dict:
+        # what the K timed steps alone give: every run prints these
+        return {
+            "metric": METRIC,
+            "value": round(value, 3),
+            "unit": "Mpixels/s",
+            "n_gpus": nsh if sharded else ws,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / frames * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (camera sweep S(120), SURVEY 8(d))",
+            "config": {"workload": f"cfg{args.config}: {cfg['desc']}"
+                                   + (" (scene table)" if scene is not None and not spec else "")
+                                   + (" (scene table, specialised)" if spec else ""), "width": W, "height": H,
+                       "bounces": cfg["bounces"], "aa": cfg["aa"],
+                       "shadow": "hard" if cfg["shadow"] == rm.RM_SHADOW_HARD else "soft",
+                       "kernel": kname, "hipgraph": bool(use_graph),
+                       "contexts_in_flight": nfl,
+                       "frames_per_launch": batch if batched else 1,
+                       "frames_in_flight": nfl * (batch if batched else 1),
+                       "communicators_per_rank": (1 if one_comm else nfl) if sharded else 0,
+                       "parallelism": (f"row-blocks of {args.row_block} x {nsh} GPUs + RCCL gather"
+                                       + (" (pipelined)" if args.pipeline else "")
+                                       + (", one process (rm_config.ngpus)" if single
+                                          else ", one process per GPU (rm_comm_init)")
+                                       if sharded else "single GPU"),
+                       "rank0_rows_per_round": (rank0_rows or args.row_block) if sharded else None,
+                       "rank0_rows_source": rank0_src if sharded else None,
+                       "shard_format": ("RGB8: 3 B per pixel gathered, alpha 255 restored by k_unshard "
+                                        "(rm_config.shard_format AUTO)") if sharded else None,
+                       "rows_per_rank": ([rm.shard_rows(H, args.row_block, nsh, s_, rank0_rows)[0]
+                                          for s_ in range(nsh)] if sharded else None)},
+            "fps": round(frames / elapsed, 3),
+            # host time to issue the K steps (rank 0): well below ms_per_step = GPU-bound
+            "host_issue_ms_per_step": round((t_issue - t0) / args.steps * 1e3, 4),
+            "spinup_ms": args.spinup_ms,
+            "full": bool(args.full),
+            "outputs": dumped,
+        }
+
+    def emit(out: dict) -> None:
+        sys.stdout.flush()
+        os.dup2(json_fd, 1)
+        print(json.dumps(out), flush=True)
+
+    # ---- --dump-outputs: the frame of the last timed step, as its context holds it ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, rs[(nstep[0] - 1) % nfl].read_rgba8())
+    if not args.full:
+        # a plain run ends here: set up, warmed up, timed, (dumped,) one line
+        if rank == 0:
+            emit(headline())
+        for rj in rs:
+            rj.close()
+        if dist_on:
+            dist.destroy_process_group()
+        return 0
+
+    # ---- --full: kernel times, phases, work counters, roofline, CPU baseline, parity ----
     kernel_ms, launches = 0.0, 0
     for rj in rs:
         ms_j, n_j = rj.kernel_time_ms(reset=True)
@@ -617,7 +744,6 @@ def main() -> int:
         launches += n_j
         rj.enable_timing(False)
     kernel_time_basis = "HIP events on the launch stream over the timed region"
-    batched = batch > 1 and not use_graph
     mean_launch_ms = None
     if nfl > 1 or batch > 1 or (use_graph and sharded):
         # Overlapping frames stretch each launch's event interval (and on a
@@ -647,7 +773,6 @@ def main() -> int:
                                 "rm_dispatch_frames" if batched else "one at a time through rm_dispatch")
                              + " (the timed region overlaps frames)")
         mean_launch_ms = kernel_ms / max(nlaunch, 1)
-    elapsed = t1 - t0
     phases = None
     rccl = None
     if sharded:
@@ -657,12 +782,6 @@ def main() -> int:
                                "(rank 0's render, the grouped gather, the assembly)")
         barrier()
         rccl = rccl_report(rs, rank, nsh if single else ws)
-    if dist_on:
-        t = torch.tensor([elapsed], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    frames = args.steps
-    value = frames * W * H / elapsed / 1e6  # whole-job Mpixels/s
 
     # ---- work counters of exactly the frames timed (untimed pass) ----
     ops_total = 0
@@ -682,11 +801,6 @@ def main() -> int:
             ops_total += algorithmic_ops(c)
             cnt_total = dict(c) if cnt_total is None else {x: cnt_total[x] + c[x] for x in c}
     mean_kernel_ms = kernel_ms / max(launches, 1)
-    kname = "k_sample" if cfg["aa"] else "k_pixel"
-    if scene is not None:
-        kname = "k_table_sample" if cfg["aa"] else "k_table_pixel"
-    if batched:
-        kname += "_frames"  # the batched kernels (grid.z = frame); PMC values per frame
     pmc, traffic_src = pmc_entry(kname if kname.endswith("_frames") else kname + "<false>",
                                  f"cfg{args.config}" + ("-spec" if spec else ""))
     traffic = int(pmc["hbm_bytes_per_launch"]) if pmc else None
@@ -763,43 +877,7 @@ def main() -> int:
 
     if rank == 0:
         out = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "Mpixels/s",
-            "n_gpus": nsh if sharded else ws,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / frames * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (camera sweep S(120), SURVEY 8(d))",
-            "config": {"workload": f"cfg{args.config}: {cfg['desc']}"
-                                   + (" (scene table)" if scene is not None and not spec else "")
-                                   + (" (scene table, specialised)" if spec else ""), "width": W, "height": H,
-                       "bounces": cfg["bounces"], "aa": cfg["aa"],
-                       "shadow": "hard" if cfg["shadow"] == rm.RM_SHADOW_HARD else "soft",
-                       "kernel": kname, "hipgraph": bool(use_graph),
-                       "contexts_in_flight": nfl,
-                       "frames_per_launch": batch if batched else 1,
-                       "frames_in_flight": nfl * (batch if batched else 1),
-                       "communicators_per_rank": (1 if one_comm else nfl) if sharded else 0,
-                       "parallelism": (f"row-blocks of {args.row_block} x {nsh} GPUs + RCCL gather"
-                                       + (" (pipelined)" if args.pipeline else "")
-                                       + (", one process (rm_config.ngpus)" if single
-                                          else ", one process per GPU (rm_comm_init)")
-                                       if sharded else "single GPU"),
-                       "rank0_rows_per_round": (rank0_rows or args.row_block) if sharded else None,
-                       "rank0_rows_source": rank0_src if sharded else None,
-                       "shard_format": ("RGB8: 3 B per pixel gathered, alpha 255 restored by k_unshard "
-                                        "(rm_config.shard_format AUTO)") if sharded else None,
-                       "rows_per_rank": ([rm.shard_rows(H, args.row_block, nsh, s_, rank0_rows)[0]
-                                          for s_ in range(nsh)] if sharded else None)},
-            "fps": round(frames / elapsed, 3),
-            # host time to issue the K steps (rank 0): well below ms_per_step = GPU-bound
-            "host_issue_ms_per_step": round((t_issue - t0) / args.steps * 1e3, 4),
-            "spinup_ms": args.spinup_ms,
+            **headline(),
             "roofline": {"bound": "valu",
                          "achieved": round(valu_issue, 3) if valu_issue else None,
                          "peak": VALU_LANE_PEAK_T, "unit": "T VALU lane-instructions/s",
@@ -848,9 +926,7 @@ def main() -> int:
             "cpu_baseline": cpu,
             "parity": parity,
         }
-        sys.stdout.flush()
-        os.dup2(json_fd, 1)
-        print(json.dumps(out), flush=True)
+        emit(out)
     for rj in rs:
         rj.close()
     if dist_on:

@@ -64,6 +64,44 @@ def test_gpus_beyond_the_visible_devices_exits_2():
     assert out.stdout.strip() == ""
 
 
+def test_steps_below_one_exit_2():
+    """--steps sets the number of timed steps: none is an error, not a division by zero."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr and out.stdout.strip() == ""
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs (bench.dump_outputs): a small frame whole, a large one as the same
+    seeded pixel sample every time, float32, under 64 MB."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 256, (54, 96, 4), dtype=np.uint8)
+    info = b.dump_outputs(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "frame_rgba8.npy")
+    assert got.dtype == np.float32 and got.shape == small.shape and (got == small).all()
+    assert sorted(os.listdir(tmp_path / "s")) == ["frame_rgba8.npy"]
+    assert info["frame_rgba8"]["shape"] == [54, 96, 4] and "sampled_pixels" not in info["frame_rgba8"]
+    # one pixel more than the limit: sampled
+    h, w = 2, b.DUMP_MAX_PIXELS // 2 + 1
+    big = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), big)
+    px = np.load(tmp_path / "a" / "frame_rgba8_pixels.npy")
+    val = np.load(tmp_path / "a" / "frame_rgba8.npy")
+    assert px.dtype == np.float64 and val.dtype == np.float32
+    assert px.shape == (b.DUMP_MAX_PIXELS,) and val.shape == (b.DUMP_MAX_PIXELS, 4)
+    idx = px.astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < h * w  # distinct, in range
+    assert (val == big.reshape(-1, 4)[idx]).all()
+    assert (px == np.load(tmp_path / "b" / "frame_rgba8_pixels.npy")).all()
+    assert (val == np.load(tmp_path / "b" / "frame_rgba8.npy")).all()
+    assert px.nbytes + val.nbytes <= 64e6
+
+
 def test_committed_pmc_entries_are_per_frame():
     """The roofline reads per-frame PMC values from profiles/ (bench.pmc_entry): every batch
     kernel it would use carries the frames per launch its summary divided by (the batched

@@ -42,7 +42,7 @@ def test_bench_rccl_path_at_world_size_one(args):
     at world size 1, plainly and from the captured per-rank graph."""
     env = dict(os.environ, RM_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], env=env,
                          cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = out.stdout.strip().splitlines()  # stdout is the JSON line alone (banners: stderr)
@@ -82,7 +82,7 @@ def test_bench_single_process_ngpus_path(args):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK",
                                                              "RM_BENCH_FORCE_DIST")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--single-process",
-                          *args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=110)
+                          "--full", *args], env=env, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
@@ -108,3 +108,35 @@ def test_bench_exits_nonzero_on_a_communicator_failure():
                          cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode == 3, (out.returncode, out.stderr[-3000:])
     assert "librm error -6" in out.stderr and out.stdout.strip() == ""
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_frame(rm, gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the K steps and prints the
+    headline line without the --full objects; --dump-outputs writes the frame the last
+    timed step rendered: sweep frame bench_frames(K)[-1], equal to a direct render."""
+    import numpy as np
+    steps, cfg = 7, 1
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK",
+                                                             "RM_BENCH_FORCE_DIST")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", "2", "--config", str(cfg), "--dump-outputs", str(tmp_path / "o")],
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-4000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == 2 and d["value"] > 0 and d["full"] is False
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    # value = W x H / ms_per_step, up to the line's rounding of ms_per_step to 1e-4 ms
+    assert abs(d["value"] * d["ms_per_step"] * 1e3 / (512 * 512) - 1) <= 0.5e-4 / d["ms_per_step"] + 1e-3
+    for k in ("roofline", "algorithmic_rate", "work", "phases", "rccl", "cpu_baseline", "parity"):
+        assert k not in d, k
+    got = np.load(tmp_path / "o" / "frame_rgba8.npy")
+    assert got.dtype == np.float32 and got.shape == (512, 512, 4)
+    assert d["outputs"]["frame_rgba8"]["shape"] == [512, 512, 4]
+    last = (steps - 1) * 120 // steps  # bench_frames(steps)[-1]
+    with rm.Renderer(512, 512, outputs=rm.RM_OUT_RGBA8, device=0) as r:
+        r.dispatch(rm.sweep_uniforms(last, 120, 0, False, rm.RM_SHADOW_HARD))
+        ref = r.read_rgba8()
+    np.testing.assert_array_equal(got, ref.astype(np.float32))
