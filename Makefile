@@ -3,6 +3,7 @@
 #   make librm      -> opengl-raymarching-in-compute-shader_amd/librm.so
 #   make oracle     -> oracle/_build/librm_oracle.so (test infrastructure)
 #   make goldens    -> oracle/_ref/gen_camera_goldens (needs /root/reference; container only)
+#   make glsl_ref   -> oracle/_ref/glsl_ref{,_glm,_ubsan}: the reference's shader as C++ (same condition)
 # Built artefacts stay in-tree (git-ignored) so they travel to the GPU box.
 
 HIPCC    ?= /opt/rocm/bin/hipcc
@@ -33,7 +34,7 @@ JIT_SRCS := rm_table.hip=$(CSRC)/rm_table.hip rm_internal.hpp=$(CSRC)/rm_interna
             rm_fastmath.hpp=$(CSRC)/rm_fastmath.hpp \
             ../../include/rm_api.h=include/rm_api.h
 
-.PHONY: all librm oracle driver goldens asan clean
+.PHONY: all librm oracle driver goldens glsl_ref asan clean
 all: librm oracle driver
 librm: $(LIBRM)
 oracle: $(ORACLE)
@@ -96,7 +97,7 @@ $(DRIVER): $(PKG)/tools/rm_frameloop.cpp include/rm/camera.hpp include/rm/input.
 # Camera goldens from the reference's vendored GLM 0.9.8.5 (third-party, in
 # /root/reference/includes/glm).  Output binary only under oracle/_ref/.
 REF ?= /root/reference
-goldens: oracle/_ref/gen_camera_goldens oracle/_ref/gen_input_goldens
+goldens: oracle/_ref/gen_camera_goldens oracle/_ref/gen_input_goldens oracle/_ref/glsl_ref oracle/_ref/glsl_ref_glm
 	oracle/_ref/gen_camera_goldens > tests/golden/camera_goldens.json
 	oracle/_ref/gen_input_goldens > tests/golden/input_goldens.json
 
@@ -107,6 +108,36 @@ oracle/_ref/gen_input_goldens: oracle/gen_input_goldens.cpp
 oracle/_ref/gen_camera_goldens: oracle/gen_camera_goldens.cpp
 	@mkdir -p oracle/_ref
 	$(CXX) -std=c++11 -O2 -ffp-contract=off -I$(REF)/includes -o $@ $<
+
+# The reference's compute shader run as C++: its text, rewritten by
+# token rules only (oracle/glsl_rewrite.py) into oracle/_ref/, compiled against
+# the reference's GLM behind oracle/glsl_prelude.hpp.  The rewritten text and the
+# binaries are the reference's program: they stay under oracle/_ref/ (git-ignored).
+#   glsl_ref        GLM's built-ins, except those DESIGN §2 defines otherwise
+#   glsl_ref_glm    GLM's built-ins only (glsl_ref_glm_mix / _minmax: one family
+#                   handed back, for tools/ref_builtin_diff.py)
+#   glsl_ref_ubsan  glsl_ref under UBSan; a stand-alone host program, run by
+#                   tests/golden/make_reference_goldens.py only
+GLSL_SRC   := $(REF)/shaders/computeShader.glsl
+GLSL_INC   := oracle/_ref/computeShader.inc
+GLSL_DEPS  := oracle/glsl_ref_main.cpp oracle/glsl_prelude.hpp include/rm_api.h $(GLSL_INC)
+GLSL_FLAGS := -std=c++20 -O2 -ffp-contract=off -isystem $(REF)/includes -DGLSL_REF_SHADER='"_ref/computeShader.inc"'
+glsl_ref: oracle/_ref/glsl_ref oracle/_ref/glsl_ref_glm oracle/_ref/glsl_ref_ubsan
+
+$(GLSL_INC): $(GLSL_SRC) oracle/glsl_rewrite.py
+	@mkdir -p oracle/_ref
+	python3 oracle/glsl_rewrite.py $< $@
+
+oracle/_ref/glsl_ref: $(GLSL_DEPS)
+	$(CXX) $(GLSL_FLAGS) -o $@ $<
+oracle/_ref/glsl_ref_glm: $(GLSL_DEPS)
+	$(CXX) $(GLSL_FLAGS) -DGLSL_REF_PURE_GLM -o $@ $<
+oracle/_ref/glsl_ref_glm_mix: $(GLSL_DEPS)
+	$(CXX) $(GLSL_FLAGS) -DGLSL_REF_GLM_MIX -o $@ $<
+oracle/_ref/glsl_ref_glm_minmax: $(GLSL_DEPS)
+	$(CXX) $(GLSL_FLAGS) -DGLSL_REF_GLM_MINMAX -o $@ $<
+oracle/_ref/glsl_ref_ubsan: $(GLSL_DEPS)
+	$(CXX) $(GLSL_FLAGS) -g -fsanitize=undefined,float-cast-overflow -o $@ $<
 
 # ---- host sanitizer build: CPU suite under ASan + UBSan ---------
 # librm's host code (the C-ABI, the table compiler and its bounds, the uniform

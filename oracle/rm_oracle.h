@@ -7,14 +7,15 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it; the
  * product (librm) never links, calls or falls back to it.
  *
- * Parity status: the GLSL itself cannot run here (no GL context, no GLSL
- * compiler) and the reference ships no tests, golden vectors or
- * fixtures.  The restatement is pinned by (1) analytic known-answer tests
- * derived from the shader text and (2) camera goldens produced from the
- * reference's vendored GLM 0.9.8.5 (oracle/gen_camera_goldens.cpp).  At the
- * GLSL built-in boundary (precision of normalize/pow/sin inside the vendor's
- * GL driver) parity is UNPINNED: the built-in semantics contract in DESIGN.md
- * defines "the reference" there.
+ * Parity status: the reference ships no tests, golden vectors or fixtures, and
+ * no GL context or GLSL compiler exists here.  The restatement is
+ * pinned by (1) the shader's own text compiled as C++ against the reference's
+ * vendored GLM 0.9.8.5 (oracle/glsl_ref_main.cpp; whole frames and single
+ * functions equal bit for bit, tests/test_reference_shader.py), (2) analytic
+ * known-answer tests derived from the shader text and (3) camera goldens from
+ * the same GLM (oracle/gen_camera_goldens.cpp).  What stays unpinned is the
+ * precision of pow/sin/sqrt inside a vendor's GL driver: the built-in
+ * semantics contract in DESIGN.md defines "the reference" there.
  */
 #ifndef RM_ORACLE_H
 #define RM_ORACLE_H

@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""What DESIGN §2's built-in choices change against GLM's own (a report, not a test).
+
+The reference's shader, compiled as C++ (oracle/glsl_ref_main.cpp), is run with
+DESIGN §2's built-ins (oracle/_ref/glsl_ref) and with one family at a time, then
+all, handed back to GLM 0.9.8.5 (oracle/glsl_prelude.hpp's -D switches):
+
+    mix            GLM: x + a*(y-x)             §2: x*(1-a) + y*a
+    min/max/clamp  GLM: x<y?x:y and x>y?x:y     §2: y<x?y:x and x<y?y:x (they differ on NaN)
+
+over the cases of tests/golden/reference_goldens.* and, with --fuzz N, the first N
+seeded random uniforms of tests/test_gpu_fuzz_uniforms.py (soft shadow, 67x41).
+Per family: the pixels that differ at all, the largest finite difference, the
+pixels that differ in RGBA8, and the pixels whose NaN mask differs.
+
+Needs the reference tree (the binaries are built from it):
+    python tools/ref_builtin_diff.py --fuzz 120 > profiles/ref_builtin_diff.txt
+"""
+import argparse
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("opengl-raymarching-in-compute-shader_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+import rmarch as rm  # noqa: E402
+import glsl_ref as G  # noqa: E402
+
+FAMILIES = [("mix", "glsl_ref_glm_mix"), ("min/max/clamp", "glsl_ref_glm_minmax"),
+            ("all (glsl_ref_glm)", "glsl_ref_glm")]
+
+
+def cases(nfuzz):
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "reference_goldens.npz"))
+    for key in sorted(gold.files):
+        if key.endswith("_uniforms"):
+            name = key[:-len("_uniforms")]
+            H, W, _ = gold[name + "_rgba32f"].shape
+            yield "fixture", name, rm.rm_uniforms.from_buffer_copy(gold[key].tobytes()), W, H
+    if nfuzz:
+        import test_gpu_fuzz_uniforms as fuzz
+        for i in range(nfuzz):
+            yield "fuzz", f"fuzz{i}", fuzz._uniforms(rm, dict(fuzz.CASES[i], sm=0)), fuzz.W, fuzz.H
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--fuzz", type=int, default=0, metavar="N",
+                    help="add the first N random uniforms of test_gpu_fuzz_uniforms (<= 256)")
+    args = ap.parse_args()
+    targets = ["oracle/_ref/glsl_ref"] + ["oracle/_ref/" + b for _, b in FAMILIES]
+    subprocess.run(["make", "-s", *targets], cwd=ROOT, check=True, stdout=subprocess.DEVNULL,
+                   stderr=subprocess.DEVNULL)
+    rows = {}  # (set, family) -> [cases, pixels, differ, max finite, rgba8 differ, nan-mask differ, worst case]
+    for kind, name, u, W, H in cases(args.fuzz):
+        base = G.frame(u, W, H)
+        for fam, binary in FAMILIES:
+            other = G.frame(u, W, H, binary=os.path.join(G.REF_DIR, binary))
+            r = rows.setdefault((kind, fam), [0, 0, 0, 0.0, 0, 0, ""])
+            differ = ~G.same_bits_or_nan(base, other)
+            both = np.isfinite(base) & np.isfinite(other)
+            d = float(np.abs(base - other)[both].max()) if both.any() else 0.0
+            r[0] += 1
+            r[1] += W * H
+            r[2] += int(differ.any(axis=2).sum())
+            if d > r[3]:
+                r[3], r[6] = d, name
+            r[4] += int((rm.quantize_rgba8(base) != rm.quantize_rgba8(other)).any(axis=2).sum())
+            r[5] += int((np.isnan(base) != np.isnan(other)).any(axis=2).sum())
+    info = G.info()
+    print(f"glsl_ref (GLM {info['glm_version']}, overrides {', '.join(info['overrides'])}) against GLM's own built-ins")
+    print(f"{'cases':<8} {'family handed to GLM':<22} {'frames':>6} {'pixels':>8} {'differ':>8} "
+          f"{'max finite |d|':>15} {'RGBA8 differ':>13} {'NaN mask differs':>17}  worst")
+    for (kind, fam), r in rows.items():
+        print(f"{kind:<8} {fam:<22} {r[0]:>6} {r[1]:>8} {r[2]:>8} {r[3]:>15.3e} {r[4]:>13} {r[5]:>17}  {r[6]}")
+
+
+if __name__ == "__main__":
+    main()
