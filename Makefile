@@ -24,9 +24,10 @@ ORACLE   := oracle/_build/librm_oracle.so
 DRIVER   := $(PKG)/rm_frameloop
 
 RM_SRCS  := $(CSRC)/rm_api.hip $(CSRC)/rm_api_comm.hip $(CSRC)/rm_api_graph.hip $(CSRC)/rm_frame_math.hip \
-            $(CSRC)/rm_kernels.hip $(CSRC)/rm_table.hip $(CSRC)/rm_jit.hip $(CSRC)/rm_host.cpp $(CSRC)/rm_comm.cpp
+            $(CSRC)/rm_kernels.hip $(CSRC)/rm_table.hip $(CSRC)/rm_jit.hip $(CSRC)/rm_host.cpp $(CSRC)/rm_comm.cpp \
+            $(CSRC)/rm_api_trace.hip $(CSRC)/rm_trace.hip $(CSRC)/rm_table_trace.hip
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
-            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp include/rm_api.h Makefile
+            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp include/rm_api.h Makefile
 # The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
 # the names they #include each other by.
 JIT_SRCS := rm_table.hip=$(CSRC)/rm_table.hip rm_internal.hpp=$(CSRC)/rm_internal.hpp \
@@ -66,6 +67,23 @@ $(PKG)/build/rm_table.o: $(CSRC)/rm_table.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
+# The ray-query kernels (rm_trace_rays) in objects of their own: each
+# includes the render kernels' source for its device code alone, with that
+# source's flags, and leaves rm_kernels.o / rm_kernels_aa.o / rm_table.o as they
+# are without it.
+$(PKG)/build/rm_trace.o: $(CSRC)/rm_trace.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(KFLAGS) -c $< -o $@
+
+# k_table_trace holds the table march twice over (the fast lanes' and the literal
+# path's): past the AMDGPU inliner's default cap on a caller's basic blocks (1100)
+# tmarch stays a call, and a call takes the staged Table and its result through
+# scratch memory (432 B per lane; none with the cap raised).
+TRACE_INLINE := -mllvm -amdgpu-inline-max-bb=8000
+$(PKG)/build/rm_table_trace.o: $(CSRC)/rm_table_trace.hip $(CSRC)/rm_table.hip $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
+
 $(PKG)/build/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
 	@mkdir -p $(dir $@)
 	python3 $(PKG)/tools/embed_sources.py $@ $(JIT_SRCS)
@@ -84,7 +102,8 @@ $(PKG)/build/rm_comm.o: $(CSRC)/rm_comm.cpp $(RM_HDRS)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(LIBRM): $(PKG)/build/rm_api.o $(PKG)/build/rm_api_comm.o $(PKG)/build/rm_api_graph.o $(PKG)/build/rm_frame_math.o \
-          $(PKG)/build/rm_kernels.o $(PKG)/build/rm_kernels_aa.o $(PKG)/build/rm_table.o $(PKG)/build/rm_jit.o $(PKG)/build/rm_host.o $(PKG)/build/rm_comm.o
+          $(PKG)/build/rm_kernels.o $(PKG)/build/rm_kernels_aa.o $(PKG)/build/rm_table.o $(PKG)/build/rm_jit.o $(PKG)/build/rm_host.o $(PKG)/build/rm_comm.o \
+          $(PKG)/build/rm_api_trace.o $(PKG)/build/rm_trace.o $(PKG)/build/rm_table_trace.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
@@ -155,9 +174,12 @@ ASANORC  := oracle/_build/librm_oracle_asan.so
 SANHOST  := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
             -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer
-ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_frame_math.o rm_kernels.o rm_kernels_aa.o rm_table.o rm_jit.o rm_host.o rm_comm.o)
+ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_frame_math.o rm_kernels.o rm_kernels_aa.o rm_table.o rm_jit.o rm_host.o rm_comm.o \
+                                      rm_api_trace.o rm_trace.o rm_table_trace.o)
 asan: $(ASANLIB) $(ASANORC)
 
+$(ASAN_DIR)/rm_trace.o: $(CSRC)/rm_kernels.hip
+$(ASAN_DIR)/rm_table_trace.o: $(CSRC)/rm_table.hip
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(RM_HDRS) $(PKG)/build/rm_jit_src.inc
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -I$(PKG)/build -c $< -o $@

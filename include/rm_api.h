@@ -377,6 +377,68 @@ int rm_kernel_time_ms(rm_ctx *ctx, double *total_ms, int64_t *launches, int rese
  * reports device 0.  RM_ERR_STATE before such a dispatch. */
 int rm_frame_phases(rm_ctx *ctx, double *render_ms, double *gather_ms, double *assemble_ms);
 
+/* ---- ray queries: caller-supplied rays against the scene ---------------------
+ * The reference marches camera rays only (castRay, glsl:68-74).  These calls run
+ * its RayMarch / GetNormal / softshadow / render on any rays: picking, depth or
+ * id under a point, line of sight to the light, collision probes, a per-pixel
+ * depth / normal / id pass.  Ray i is (origins[i], dirs[i]), [n][3] floats each;
+ * hit i is one rm_ray_hit.
+ *
+ *  - A query uses the context's current uniforms and scene at the time of the
+ *    call: iTime drives the blend; the light and camera.pos feed getPointLight
+ *    (its view vector) under RM_TRACE_SHADE; bounceVar and shadow_mode apply as in
+ *    a dispatch; the scene is the built-in one or the rm_set_scene table (a
+ *    context with rm_scene_specialize on traces with the generic table code).
+ *    The uniforms are checked as rm_set_uniforms checks them.
+ *  - rd is NOT normalised and need not be unit length: t is the GLSL's parameter
+ *    along rd as given, the point ro + rd * t (what RayMarch does, glsl:125-142).
+ *  - Every input, of any value, gives the reference's result: zero, huge,
+ *    infinite and NaN ro or rd included.
+ *  - Queries are ordered on the context's stream (rm_set_stream's when one is
+ *    set) after the dispatches already queued.  They touch neither the
+ *    context's images nor its counters nor its batch ring, and are not part of
+ *    graph replay.  A context with cfg.counters traces with the production device
+ *    code and leaves rm_counters alone.  With rm_enable_timing on, a trace launch
+ *    is bracketed and counted like a render launch.
+ *  - The rays of one wave are 64 consecutive indices: a caller that wants speed
+ *    keeps neighbouring rays neighbouring; any order is correct.
+ *  - A sharded context, or one of an rm_comm_init communicator, traces locally:
+ *    the call is not collective.  A multi-device context (cfg.ngpus >= 1):
+ *    RM_ERR_STATE.
+ *
+ * Returns: n == 0 is RM_OK and writes nothing.  RM_ERR_INVALID for a null
+ * pointer with n > 0, n < 0 or n > 2^31 - 1, a hits_dev that is not 16-byte
+ * aligned, unknown flag bits, RM_TRACE_SHADOW combined with any other flag,
+ * RM_TRACE_SHADE | RM_TRACE_REFLECTED, and rm_pick outside the frame. */
+#define RM_HAS_TRACE 1
+/* rm_trace flags */
+#define RM_TRACE_HIT       0  /* RayMarch(ro, rd) glsl:125-142: t, id, material, albedo */
+#define RM_TRACE_REFLECTED 1  /* reflectedRay's limits instead (256 steps, tmax 200; glsl:144-161) */
+#define RM_TRACE_NORMAL    2  /* + GetNormal(ro + rd*t) on a hit (glsl:278-288) */
+#define RM_TRACE_SHADE     4  /* + render(ro, rd) glsl:218-251: the colour a pixel sample with this ray gets */
+#define RM_TRACE_SHADOW    8  /* alone: t = softshadow(ro, rd, k) glsl:201-216, k from shadow_mode */
+
+typedef struct rm_ray_hit {   /* 48 bytes */
+  float   t;          /* RayHit.hitpoint; -1 = miss (the GLSL's dummy).  SHADOW: the shadow factor */
+  int32_t id;         /* RayHit.id; -1 on a miss */
+  float   material;   /* RayHit.material; 1.0 on a miss (the dummy's) */
+  float   albedo[3];  /* RayHit.color (checkers(p) for the floor); 0 on a miss */
+  float   normal[3];  /* RM_TRACE_NORMAL and a hit, else 0 */
+  float   color[3];   /* RM_TRACE_SHADE, else 0 */
+} rm_ray_hit;
+
+/* Host rays and hits; synchronous (upload, trace, download through staging
+ * buffers the context owns, grown on demand, freed by rm_destroy). */
+int rm_trace_rays(rm_ctx *ctx, const float *origins, const float *dirs, int64_t n, uint32_t flags, rm_ray_hit *hits);
+/* Device pointers; asynchronous on the context's stream.  hits_dev: 16-byte aligned. */
+int rm_trace_rays_device(rm_ctx *ctx, const void *origins_dev, const void *dirs_dev, int64_t n, uint32_t flags,
+                         void *hits_dev);
+/* The ray of pixel (px, py) of the context's frame as a frame without
+ * supersampling casts it: uv = (2 p - dims) / dims (glsl:301-305), castRay with
+ * the current camera; flags RM_TRACE_HIT | RM_TRACE_NORMAL; synchronous.  Row 0 is
+ * the bottom row: a window cursor's y maps to height - 1 - y. */
+int rm_pick(rm_ctx *ctx, int32_t px, int32_t py, rm_ray_hit *hit);
+
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process
  * per GPU (torch.distributed.run, MPI).  Rank 0 creates an id and broadcasts it

@@ -179,10 +179,11 @@ void free_all(rm_ctx* c) {
   c->comm = nullptr;
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, (void**)&c->d_counts, (void**)&c->d_counters,
-                   (void**)&c->d_uv, (void**)&c->d_scene}) {
+                   (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
+  c->trace_cap = 0;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);
   for (float* p : c->ring32) (void)hipFree(p);
@@ -215,15 +216,15 @@ void free_all(rm_ctx* c) {
   c->stream = nullptr;
 }
 
-int check_uniforms(rm_ctx* c, const rm_uniforms& u) {
+}  // namespace
+
+int rm::check_uniforms(rm_ctx* c, const rm_uniforms& u) {
   if (u.bounceVar < 0 || u.bounceVar > 5)
     return fail(c, RM_ERR_INVALID, "bounceVar must be in 0..5 (main.cpp:199-204)");
   if (u.shadow_mode != RM_SHADOW_SOFT && u.shadow_mode != RM_SHADOW_HARD)
     return fail(c, RM_ERR_INVALID, "shadow_mode must be RM_SHADOW_SOFT or RM_SHADOW_HARD");
   return RM_OK;
 }
-
-}  // namespace
 
 #ifdef RM_STATS
 namespace rm {

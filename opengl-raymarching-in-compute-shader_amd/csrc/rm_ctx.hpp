@@ -1,6 +1,7 @@
 // rm_ctx.hpp — the context, and what the files of librm's C-ABI share:
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
-// rm_api_comm.hip (RCCL-gathered frames) and rm_api_graph.hip (hipGraph replay).
+// rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay)
+// and rm_api_trace.hip (ray queries).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -29,6 +30,11 @@ hipError_t launch_unshard(const void* gathered, void* frame, int width, int heig
                           int row_block0, int nshards, int rows_cap, hipStream_t s, size_t rank_stride_rows = 0,
                           bool rgb3 = false);
 hipError_t launch_frames(const rmd::FrameBatch& B, int n, hipStream_t s);
+// ray queries (rm_trace.hip, rm_table_trace.hip): n >= 1 rays, device pointers
+hipError_t launch_trace(const rmd::Frame& F, const void* origins, const void* dirs, void* hits, int64_t n,
+                        uint32_t flags, hipStream_t s);
+hipError_t launch_table_trace(const rmd::Frame& F, const void* origins, const void* dirs, void* hits,
+                              int64_t n, uint32_t flags, hipStream_t s);
 
 // Which kernel renders a frame (rm_api.hip pick_kernel): the built-in scene's, or
 // for a runtime scene table its specialised kernels (jit) or the generic table
@@ -134,6 +140,10 @@ struct rm_ctx {
   hipEvent_t gdone = nullptr;       // the last batch's work on gstream
   hipEvent_t out_ev = nullptr;      // rm_wait_output: the tail of the context's stream
   bool gdone_pending = false;       // plain dispatches order after it
+  // rm_trace_rays' staging buffers, grown on demand: [cap] origins then [cap] dirs; [cap] rm_ray_hit
+  float* d_trace_rays = nullptr;
+  void* d_trace_hits = nullptr;
+  int64_t trace_cap = 0;
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;
@@ -202,6 +212,7 @@ struct KeepDevice {
 
 // ---- rm_api.hip: context and dispatch --------------------------------------------------
 int set_device(rm_ctx* c);
+int check_uniforms(rm_ctx* c, const rm_uniforms& u);
 // The end of a failed rm_create: c's error becomes the creation error, c is freed.
 int create_fail(rm_ctx* c, int code);
 rmd::Frame make_frame(const rm_ctx* c);

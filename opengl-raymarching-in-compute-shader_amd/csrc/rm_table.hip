@@ -1503,7 +1503,8 @@ __global__ __launch_bounds__(64, SL ? RM_TABLE_SL_WAVES : RM_TABLE_MIN_WAVES) vo
 
 }  // namespace rmd
 
-#ifndef RM_TABLE_STATIC
+// (RM_TABLE_DEVICE_ONLY: rm_table_trace.hip includes this file for the device code above alone)
+#if !defined(RM_TABLE_STATIC) && !defined(RM_TABLE_DEVICE_ONLY)
 namespace rm {
 
 namespace {

@@ -45,6 +45,13 @@ RM_KERNEL_PIXEL = 1
 RM_SHARD_AUTO = 0   # RGB8 shards once the context gathers, RGBA8 otherwise (rm_config.shard_format)
 RM_SHARD_RGBA8 = 1
 RM_SHARD_RGB8 = 2
+# ray queries (rm_trace_rays): flags
+RM_HAS_TRACE = 1
+RM_TRACE_HIT = 0        # RayMarch(ro, rd): t, id, material, albedo
+RM_TRACE_REFLECTED = 1  # reflectedRay's limits instead (256 steps, tmax 200)
+RM_TRACE_NORMAL = 2     # + GetNormal(ro + rd t) on a hit
+RM_TRACE_SHADE = 4      # + render(ro, rd): the colour a pixel sample with this ray gets
+RM_TRACE_SHADOW = 8     # alone: t = softshadow(ro, rd, k)
 
 
 class RMError(RuntimeError):
@@ -110,6 +117,17 @@ class rm_primitive(C.Structure):
     _fields_ = [("type", C.c_int32), ("swizzle", C.c_int32), ("id", C.c_int32),
                 ("paint", C.c_int32), ("material", C.c_float), ("color", C.c_float * 3),
                 ("center", C.c_float * 3), ("param", C.c_float * 7)]
+
+
+class rm_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("id", C.c_int32), ("material", C.c_float),
+                ("albedo", C.c_float * 3), ("normal", C.c_float * 3), ("color", C.c_float * 3)]
+
+
+# rm_ray_hit as a numpy record (Renderer.trace's result for host rays)
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("id", "<i4"), ("material", "<f4"), ("albedo", "<f4", (3,)),
+                          ("normal", "<f4", (3,)), ("color", "<f4", (3,))])
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(rm_ray_hit) == 48
 
 
 # runtime scene table (include/rm_api.h)
@@ -241,6 +259,9 @@ _SIGS = {
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rm_comm_set_timeout": (C.c_int, [_P, C.c_int32]),
     "rm_comm_check": (C.c_int, [_P]),
+    "rm_trace_rays": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
+    "rm_trace_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
+    "rm_pick": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(rm_ray_hit)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -582,6 +603,46 @@ class Renderer:
         out = np.empty((self.rows, self.width), np.uint32)
         _check(lib().rm_read_sdf_counts(self._h, out.ctypes.data), self._h)
         return out
+
+    # -- ray queries (rm_trace_rays)
+    def trace(self, origins, dirs, flags: int = RM_TRACE_HIT):
+        """Trace rays (origins[i], dirs[i]) against the scene with the current uniforms.
+
+        numpy (n, 3) float32 arrays: synchronous, returns a RAY_HIT_DTYPE array of n records
+        (rm_trace_rays).  torch device tensors, (n, 3) float32 contiguous: asynchronous on the
+        context's stream (set_stream), returns an (n, 12) float32 device tensor holding the
+        rm_ray_hit records, `id` as its bits (rm_trace_rays_device; no copy is made).  dirs
+        are not normalised: t is the parameter along dirs[i] as given."""
+        if not isinstance(origins, np.ndarray) and hasattr(origins, "data_ptr"):
+            import torch
+            for x in (origins, dirs):
+                if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+                        and x.dim() == 2 and x.shape[1] == 3):
+                    raise ValueError("trace: device rays must be contiguous (n, 3) float32 tensors")
+            if origins.shape != dirs.shape or origins.device != dirs.device:
+                raise ValueError("trace: origins and dirs differ in shape or device")
+            n = int(origins.shape[0])
+            hits = torch.empty((n, 12), dtype=torch.float32, device=origins.device)
+            _check(lib().rm_trace_rays_device(self._h, origins.data_ptr(), dirs.data_ptr(), n,
+                                              int(flags), hits.data_ptr()), self._h)
+            return hits
+        o = np.ascontiguousarray(origins, np.float32)
+        d = np.ascontiguousarray(dirs, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("trace: origins and dirs must both be (n, 3)")
+        hits = np.empty(o.shape[0], RAY_HIT_DTYPE)
+        _check(lib().rm_trace_rays(self._h, o.ctypes.data, d.ctypes.data, o.shape[0], int(flags),
+                                   hits.ctypes.data), self._h)
+        return hits
+
+    def pick(self, px: int, py: int) -> np.ndarray:
+        """What pixel (px, py) of this context's frame shows (rm_pick): one RAY_HIT_DTYPE
+        record with the hit and its normal.  Row 0 is the bottom row: a window cursor's y
+        maps to height - 1 - y."""
+        hit = np.zeros(1, RAY_HIT_DTYPE)
+        _check(lib().rm_pick(self._h, int(px), int(py),
+                             C.cast(hit.ctypes.data, C.POINTER(rm_ray_hit))), self._h)
+        return hit[0]
 
     # -- device interop
     def set_stream(self, stream_ptr: Optional[int]) -> None:

@@ -1,0 +1,43 @@
+"""The ray-query kernels of the in-tree build (make librm, __graft_entry__.build):
+k_trace and k_table_trace use no scratch memory (their kernel descriptors'
+private segment), and live in objects of their own, so the render kernels'
+objects hold no trace kernel."""
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "build")
+OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+
+
+def _private_sizes(obj, tmp_path):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_scene_table import _kernel_private_sizes
+    src = os.path.join(BUILD, obj)
+    if not os.path.exists(src):
+        pytest.skip("librm not built")
+    d = tmp_path / obj
+    d.mkdir()
+    shutil.copy(src, d / "x.o")
+    subprocess.run([OBJDUMP, "--offloading", "x.o"], cwd=d, capture_output=True, check=True)
+    cos = [p for p in os.listdir(d) if "gfx950" in p]
+    assert len(cos) == 1, os.listdir(d)
+    return _kernel_private_sizes(open(d / cos[0], "rb").read())
+
+
+@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
+@pytest.mark.parametrize("obj,kernel", [("rm_trace.o", "7k_traceE"), ("rm_table_trace.o", "13k_table_traceE")])
+def test_trace_kernels_use_no_scratch(obj, kernel, tmp_path):
+    priv = _private_sizes(obj, tmp_path)
+    assert list(priv) and all(kernel in k for k in priv), priv  # the object's only kernel
+    assert all(v == 0 for v in priv.values()), priv
+
+
+@pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
+@pytest.mark.parametrize("obj", ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o"])
+def test_render_objects_hold_no_trace_kernel(obj, tmp_path):
+    assert not [k for k in _private_sizes(obj, tmp_path) if "trace" in k]
