@@ -55,6 +55,7 @@ extern "C" {
 /* ---- output image formats (bitmask for rm_config.outputs) ----------------- */
 #define RM_OUT_RGBA8 1   /* display format (what the quad shows, Quad.glsl:21-25) */
 #define RM_OUT_RGBA32F 2 /* the reference texture's true storage (texture.cpp:19) */
+/* (RM_OUT_GBUFFER 4, every pixel's primary hit: the G-buffer section below) */
 
 /* ---- RGBA8 shard image formats (rm_config.shard_format, API version 6) ----
  * The reference stores alpha = 1.0 in every pixel (finalColor = vec4(render(),
@@ -438,6 +439,56 @@ int rm_trace_rays_device(rm_ctx *ctx, const void *origins_dev, const void *dirs_
  * the current camera; flags RM_TRACE_HIT | RM_TRACE_NORMAL; synchronous.  Row 0 is
  * the bottom row: a window cursor's y maps to height - 1 - y. */
 int rm_pick(rm_ctx *ctx, int32_t px, int32_t py, rm_ray_hit *hit);
+
+/* ---- G-buffer: every pixel's primary hit, from the frame kernels themselves ----
+ * The reference's author wanted a normal and a depth view of the frame (both
+ * commented out in render(), glsl:229, 248-249).  With RM_OUT_GBUFFER in
+ * rm_config.outputs (with RM_OUT_RGBA8 and/or RM_OUT_RGBA32F, or alone) the
+ * context owns a third image, [rows][width] of rm_gbuffer_px (rows: the height,
+ * or a shard's rows_cap; row 0 is the bottom row, as for the colour images), and
+ * every rm_dispatch writes it from the primary hit the frame kernel holds anyway:
+ * the price of its stores, not of a second march (rm_trace_rays_device over the
+ * frame's rays marches every ray again).
+ *
+ *  - A record holds rm_ray_hit's fields of the same names with the same miss
+ *    values, so it compares field by field with a RM_TRACE_HIT | RM_TRACE_NORMAL
+ *    trace of the pixel's ray.  `material` is left out to keep the record at 32
+ *    bytes (two 16-byte stores per pixel): it is 0 for id 7 of the built-in
+ *    scene, and the table entry's for a table.
+ *  - Which ray: without supersampling the pixel's one castRay ray, the ray rm_pick
+ *    casts.  With AA on, the FIRST sample's ray: uv after the first offset pair,
+ *    (2 p - dims) / dims + 0.25 / dims (glsl:311-313).  The supersampling kernel
+ *    casts no centre ray; t, id, normal and albedo are one sample's, not averages.
+ *  - The padding rows of a sharded context hold the miss record.
+ *  - The colour images are what they are without the bit, bit for bit.
+ *  - This version: rm_dispatch on a one-device context, whole or row-sharded
+ *    (nshards > 1 without a communicator); the built-in scene and rm_set_scene
+ *    tables; AA on and off; every bounceVar and shadow_mode.  rm_create refuses
+ *    the bit together with cfg.counters or cfg.ngpus >= 1 (RM_ERR_INVALID).  On a
+ *    G-buffer context rm_dispatch_frames, rm_graph_enable(ctx, 1),
+ *    rm_graph_dispatch and rm_comm_init return RM_ERR_STATE.
+ *  - rm_scene_specialize on a G-buffer context: accepted, but tables render
+ *    through the generic table code (as ray queries do), no kernel is compiled
+ *    and rm_scene_kernel_waves reports 0.  The images are the same. */
+#define RM_HAS_GBUFFER 1
+#define RM_OUT_GBUFFER 4 /* rm_config.outputs: the per-pixel primary hit (rm_gbuffer_px) */
+
+typedef struct rm_gbuffer_px {  /* 32 bytes */
+  float   t;          /* RayHit.hitpoint of the pixel's primary ray; -1 = miss */
+  int32_t id;         /* RayHit.id; -1 on a miss */
+  float   normal[3];  /* GetNormal(ro + rd*t) on a hit, else 0 */
+  float   albedo[3];  /* RayHit.color (checkers(p) on the floor); 0 on a miss */
+} rm_gbuffer_px;
+
+/* Synchronous readback of the last dispatch's G-buffer; row_pitch (bytes, 0 =
+ * width * 32), flip_y and the shard rules are rm_read_rgba32f's.  RM_ERR_STATE
+ * without RM_OUT_GBUFFER or before the first dispatch. */
+int rm_read_gbuffer(rm_ctx *ctx, rm_gbuffer_px *dst, size_t row_pitch, int flip_y);
+/* Render the G-buffer into a caller-owned device buffer of rows * width * 32
+ * bytes, 16-byte aligned (else RM_ERR_INVALID); NULL restores the context's own.
+ * rm_wait_output and rm_synchronize order it like the colour images. */
+int rm_set_output_gbuffer(rm_ctx *ctx, void *device_ptr);
+int rm_get_output_gbuffer(rm_ctx *ctx, void **device_ptr);
 
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process

@@ -146,6 +146,8 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
   RenderKernel k;
   k.aa = F.aa;
   k.table = c->nprims != 0;
+  k.gbuf = has_gbuf(c);
+  if (k.gbuf) return k;
   if (!k.table || (k.jit = frame_jit(c, F))) return k;
   // the generic table kernel's instance (rm_table.hip launch_table): the lazy
   // slots it holds (EX_NSLOTS of the compiled words fit) and its production
@@ -157,7 +159,12 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
   return k;
 }
 
-hipError_t rm::launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s) {
+hipError_t rm::launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s, void* gbuf) {
+  if (k.gbuf) {
+    // (rm_create refuses counters with the bit; a missing image is an error, not a plain frame)
+    if (!gbuf || counters) return hipErrorInvalidValue;
+    return k.table ? rm::launch_table_gbuf(F, gbuf, s) : rm::launch_gbuf(F, gbuf, s);
+  }
   if (!k.table) return rm::launch_pixel(F, counters, s);
   if (k.jit) return rm::launch_table_jit(k.jit, F, counters, s);
   return rm::launch_table(F, counters, s, k.nslots, k.shape);
@@ -178,7 +185,7 @@ void free_all(rm_ctx* c) {
   c->subs.clear();
   c->comm = nullptr;
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
-                   (void**)&c->d_rgba8, (void**)&c->d_rgba32f, (void**)&c->d_counts, (void**)&c->d_counters,
+                   (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
                    (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
@@ -288,8 +295,10 @@ int rm_create(rm_ctx** out, const rm_config* cfg) {
       return fail(nullptr, RM_ERR_INVALID, "rm_create: unknown kernel variant");
     return create_multi(out, cfg);
   }
-  if (cfg->outputs & ~(RM_OUT_RGBA8 | RM_OUT_RGBA32F))
+  if (cfg->outputs & ~(RM_OUT_RGBA8 | RM_OUT_RGBA32F | RM_OUT_GBUFFER))
     return fail(nullptr, RM_ERR_INVALID, "rm_create: unknown output bits");
+  if ((cfg->outputs & RM_OUT_GBUFFER) && cfg->counters)
+    return fail(nullptr, RM_ERR_INVALID, "rm_create: RM_OUT_GBUFFER is not available with counters");
   if (cfg->kernel < RM_KERNEL_AUTO || cfg->kernel > RM_KERNEL_PIXEL)
     return fail(nullptr, RM_ERR_INVALID, "rm_create: unknown kernel variant");
   if (cfg->nshards > 1 && rm_shard_rows(cfg->height, cfg->row_block, cfg->rank0_rows, cfg->nshards, cfg->shard,
@@ -339,6 +348,12 @@ int rm_create(rm_ctx** out, const rm_config* cfg) {
   if (c->cfg.outputs & RM_OUT_RGBA32F) {
     if ((e = hipMalloc(&c->d_rgba32f, npx * 16)) != hipSuccess) return bail(hip_fail(c, e, "hipMalloc rgba32f"));
     if ((e = hipMemsetAsync(c->d_rgba32f, 0, npx * 16, c->stream)) != hipSuccess)
+      return bail(hip_fail(c, e, "hipMemset"));
+  }
+  if (has_gbuf(c)) {
+    if ((e = hipMalloc(&c->d_gbuf, npx * sizeof(rm_gbuffer_px))) != hipSuccess)
+      return bail(hip_fail(c, e, "hipMalloc gbuffer"));
+    if ((e = hipMemsetAsync(c->d_gbuf, 0, npx * sizeof(rm_gbuffer_px), c->stream)) != hipSuccess)
       return bail(hip_fail(c, e, "hipMemset"));
   }
   if (c->cfg.counters) {
@@ -487,7 +502,7 @@ int rm::render_launch(rm_ctx* c) {
   hipEvent_t e0, e1;
   if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
   if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
-  const hipError_t e = launch(pick_kernel(c, F), F, c->cfg.counters != 0, c->stream);
+  const hipError_t e = launch(pick_kernel(c, F), F, c->cfg.counters != 0, c->stream, image_gbuf(c));
   if (e != hipSuccess) return hip_fail(c, e, "kernel launch");
   if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
   c->dispatched = true;
@@ -624,6 +639,7 @@ int rm_dispatch_frames(rm_ctx* c, const rm_uniforms* u, int32_t n) {
     if (rc != RM_OK) return rc;
   }
   if (c->cfg.counters) return fail(c, RM_ERR_STATE, "rm_dispatch_frames: not available with counters");
+  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, "rm_dispatch_frames: not available on a G-buffer context (RM_OUT_GBUFFER)");
   // launch_batch walks c->u (and every member's) through the frames; a failed
   // batch leaves the uniforms of the last successful dispatch
   const rm_uniforms before = c->u;
@@ -645,10 +661,11 @@ int rm_synchronize(rm_ctx* c) {
   return stream_wait(c);
 }
 
+}  // extern "C"
+
 // packed3: `dev` is an RGB8 shard image (rows of width x 3 bytes), read back as
 // RGBA8 with alpha 255 (rm_config.shard_format).
-static int read_image(rm_ctx* c, const void* dev, size_t bpp, void* dst, size_t row_pitch,
-                      int flip_y, bool packed3 = false) {
+int rm::read_image(rm_ctx* c, const void* dev, size_t bpp, void* dst, size_t row_pitch, int flip_y, bool packed3) {
   if (!c || !dst) return RM_ERR_INVALID;
   if (!dev) return fail(c, RM_ERR_STATE, "output format not enabled in rm_config.outputs");
   if (!c->dispatched) return fail(c, RM_ERR_STATE, "no dispatch yet");
@@ -698,6 +715,8 @@ static int read_image(rm_ctx* c, const void* dev, size_t bpp, void* dst, size_t 
   }
   return RM_OK;
 }
+
+extern "C" {
 
 int rm_read_rgba8(rm_ctx* c, uint8_t* dst, size_t row_pitch, int flip_y) {
   if (!c) return RM_ERR_INVALID;
@@ -795,7 +814,7 @@ int rm_set_scene(rm_ctx* c, const rm_primitive* prims, int32_t n) {
   if (rc != RM_OK) return rc;
   // compile first: a table whose specialisation fails leaves the context as it was
   const rm::JitTable* jit = nullptr;
-  if (c->specialize) {
+  if (c->specialize && !has_gbuf(c)) {  // (a G-buffer context renders tables with the generic code)
     std::string err;
     if ((rc = rm::jit_table(words.data(), n, &jit, err)) != RM_OK) return fail(c, rc, err);
     if (!jit->mod) jit = nullptr;  // no spill-free bound: the generic kernel
@@ -844,7 +863,8 @@ int rm_scene_specialize(rm_ctx* c, int enable) {
     c->jit = nullptr;
     return RM_OK;
   }
-  if (!c->nprims || c->jit) return RM_OK;
+  // a G-buffer context renders tables with the generic code: nothing to compile
+  if (!c->nprims || c->jit || has_gbuf(c)) return RM_OK;
   int rc = set_device(c);
   if (rc != RM_OK) return rc;
   std::string err;

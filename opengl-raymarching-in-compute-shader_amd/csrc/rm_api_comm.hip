@@ -197,6 +197,9 @@ int comm_attach(rm_ctx* c, ncclComm_t comm, int rank, int n, bool own, bool memb
 }
 
 int check_comm_config(const rm_config& cfg, const char* who) {
+  if (cfg.outputs & RM_OUT_GBUFFER)
+    return fail(nullptr, RM_ERR_INVALID, std::string(who) + ": RM_OUT_GBUFFER is not available for "
+                                         "RCCL-gathered frames (a one-device context only)");
   if ((cfg.outputs & ~(RM_OUT_RGBA8 | RM_OUT_RGBA32F)) != 0 || cfg.counters)
     return fail(nullptr, RM_ERR_INVALID, std::string(who) + ": RCCL-gathered frames are RGBA8 and/or "
                                          "RGBA32F, without counters");
@@ -617,6 +620,7 @@ int rm_comm_init(rm_ctx* c, const void* id, int32_t nranks, int32_t rank) {
   if (!c || !id) return RM_ERR_INVALID;
   if (!c->subs.empty()) return fail(c, RM_ERR_STATE, "a multi-GPU context has its own communicator");
   if (c->comm) return fail(c, RM_ERR_STATE, "the context already has a communicator");
+  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, "rm_comm_init: not available on a G-buffer context (RM_OUT_GBUFFER)");
   // an aborted context can only be destroyed (rm_api.h); a second init would
   // re-attach without freeing its gather buffers
   if (c->comm_failed) return comm_dead(c);

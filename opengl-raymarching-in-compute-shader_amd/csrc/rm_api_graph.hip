@@ -125,12 +125,14 @@ int rm_graph_enable(rm_ctx* c, int enable) {
     return RM_OK;
   }
   if (c->cfg.counters) return fail(c, RM_ERR_STATE, "graph path does not collect counters");
+  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, "rm_graph_enable: not available on a G-buffer context (RM_OUT_GBUFFER)");
   c->graph_on = true;
   return RM_OK;
 }
 
 int rm_graph_dispatch(rm_ctx* c) {
   if (!c) return RM_ERR_INVALID;
+  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, "rm_graph_dispatch: not available on a G-buffer context (RM_OUT_GBUFFER)");
   if (!c->graph_on) return fail(c, RM_ERR_STATE, "rm_graph_enable(ctx, 1) first");
   if (!c->subs.empty()) return multi_frame(c, true);
   return graph_frame(c);

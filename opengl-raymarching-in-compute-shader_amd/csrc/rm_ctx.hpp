@@ -1,7 +1,7 @@
 // rm_ctx.hpp — the context, and what the files of librm's C-ABI share:
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
-// rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay)
-// and rm_api_trace.hip (ray queries).
+// rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
+// rm_api_trace.hip (ray queries) and rm_api_gbuffer.hip (the G-buffer image).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -35,18 +35,26 @@ hipError_t launch_trace(const rmd::Frame& F, const void* origins, const void* di
                         uint32_t flags, hipStream_t s);
 hipError_t launch_table_trace(const rmd::Frame& F, const void* origins, const void* dirs, void* hits,
                               int64_t n, uint32_t flags, hipStream_t s);
+// the frame kernels with the G-buffer output (rm_gbuffer.hip, rm_table_gbuffer.hip):
+// gbuf is a 16-byte aligned device pointer to F.rows * F.width rm_gbuffer_px
+hipError_t launch_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
+hipError_t launch_table_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
 
 // Which kernel renders a frame (rm_api.hip pick_kernel): the built-in scene's, or
 // for a runtime scene table its specialised kernels (jit) or the generic table
 // kernel's instance (nslots, shape: rm_table.hip launch_table).  Frames of one
-// RenderKernel share a launch of a batch, and a captured graph.
+// RenderKernel share a launch of a batch, and a captured graph.  A G-buffer
+// context (RM_OUT_GBUFFER) renders with the G-buffer kernels: one for the
+// built-in scene, one for every table (jit null, nslots and shape unused).
 struct RenderKernel {
   bool table = false;
+  bool gbuf = false;
   int aa = 0;                   // the grid shape depends on it
   const JitTable* jit = nullptr;
   int nslots = 0, shape = 0;    // the generic table kernel's instance (jit null)
   bool operator==(const RenderKernel& o) const {
-    return table == o.table && aa == o.aa && jit == o.jit && nslots == o.nslots && shape == o.shape;
+    return table == o.table && gbuf == o.gbuf && aa == o.aa && jit == o.jit && nslots == o.nslots &&
+           shape == o.shape;
   }
   // The launched kernel's argument is a FrameBatch, not a Frame: every table
   // production kernel renders a single frame as a batch of one (rm_table.hip
@@ -83,6 +91,8 @@ struct rm_ctx {
   // moves them, k_unshard expands them with alpha 255
   bool rgb3 = false;
   float* d_rgba32f = nullptr;
+  void* d_gbuf = nullptr;         // own G-buffer image (RM_OUT_GBUFFER): [rows][width] rm_gbuffer_px
+  void* ext_gbuf = nullptr;       // caller-provided one (rm_set_output_gbuffer)
   uint32_t* d_counts = nullptr;
   unsigned long long* d_counters = nullptr;
   float* d_uv = nullptr;          // per-column / per-row uv table (Frame::uvx / uvy)
@@ -187,6 +197,13 @@ inline float* image_rgba32f(const rm_ctx* c) {
   if (comm_root(c)) return c->d_frame32;
   return render_dst32(c);
 }
+// A G-buffer context has no communicator and no devices of its own: it renders
+// into, and reads, one image.
+inline bool has_gbuf(const rm_ctx* c) { return (c->cfg.outputs & RM_OUT_GBUFFER) != 0; }
+inline void* image_gbuf(const rm_ctx* c) {
+  if (!has_gbuf(c)) return nullptr;
+  return c->ext_gbuf ? c->ext_gbuf : c->d_gbuf;
+}
 inline int image_rows(const rm_ctx* c) {
   if (!c->subs.empty() || comm_root(c)) return c->cfg.height;
   return c->rows;
@@ -217,8 +234,9 @@ int check_uniforms(rm_ctx* c, const rm_uniforms& u);
 int create_fail(rm_ctx* c, int code);
 rmd::Frame make_frame(const rm_ctx* c);
 RenderKernel pick_kernel(const rm_ctx* c, const rmd::Frame& F);
-// One frame, with or without counters; the frames B.f[0..n) of one RenderKernel.
-hipError_t launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s);
+// One frame, with or without counters (gbuf: the G-buffer image of a k.gbuf
+// kernel); the frames B.f[0..n) of one RenderKernel.
+hipError_t launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s, void* gbuf = nullptr);
 hipError_t launch(const RenderKernel& k, const rmd::FrameBatch& B, int n, hipStream_t s);
 int timing_events(rm_ctx* c, hipEvent_t* e0, hipEvent_t* e1);
 int order_after_batch(rm_ctx* c);
@@ -226,6 +244,9 @@ int render_launch(rm_ctx* c);
 int phase(rm_ctx* c, int k, hipStream_t st = nullptr);
 int ensure_ring(rm_ctx* c, int n, int rows);
 int launch_batch(rm_ctx* c, const rm_uniforms* u, int n, uint8_t* const* out8, float* const* out32);
+// Synchronous readback of a [image_rows][width] device image of bpp bytes per pixel.
+int read_image(rm_ctx* c, const void* dev, size_t bpp, void* dst, size_t row_pitch, int flip_y,
+               bool packed3 = false);
 
 // ---- rm_api_comm.hip: RCCL-gathered frames -----------------------------------------------
 long default_comm_timeout_ms();

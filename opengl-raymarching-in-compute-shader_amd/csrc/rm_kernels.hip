@@ -390,9 +390,10 @@ __device__ f3 bounce(const Frame& F, f3 rayDir, f3 pos, f3 normal, f3 color, f3 
   return color;
 }
 
-// render glsl:218-251
-template <bool COUNT, bool PPROJ = false>
-__device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c) {
+// render glsl:218-251.  hit: where the primary hit goes besides (rm_scene.hpp NoHit /
+// GbufStore), called once: after the normal on a hit, after the march on a miss.
+template <bool COUNT, bool PPROJ = false, class HIT = NoHit>
+__device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT hit = HIT()) {
   f3 color = subs(mk(0.30f, 0.36f, 0.60f), rd.y * 0.2f);
   int id;
   f3 hcol;
@@ -408,10 +409,14 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c) {
   }
 #endif
   RM_STAT(30);
+  if constexpr (wants_hit<HIT>::value) {
+    if (th == -1.0f) hit(th, id, mk(0.0f, 0.0f, 0.0f), hcol);  // march's miss: id -1, colour 0
+  }
   if (th != -1.0f) {
     RM_STAT(31);
     f3 pos = add(ro, muls(rd, th));
     f3 normal = get_normal<COUNT, true>(F, pos, c, dl);
+    if constexpr (wants_hit<HIT>::value) hit(th, id, normal, hcol);
     if (COUNT) c.lights++;
     float ldist;
     color = point_light(F, hcol, normal, pos, &ldist);
@@ -447,8 +452,9 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c) {
 // waiting for its workgroup's slowest wave.  This replaces the reference's
 // 39x39 tiles; its W/wg truncation band (main.cpp:123) is not reproduced.
 constexpr int kTileW = 8, kTileH = 8;
-template <bool COUNT>
-__device__ __forceinline__ void pixel_body(const Frame& F, int rowslot) {
+// GBUF: the pixel's rm_gbuffer_px goes to gbuf as well (k_gbuf_pixel, rm_gbuffer.hip).
+template <bool COUNT, bool GBUF = false>
+__device__ __forceinline__ void pixel_body(const Frame& F, int rowslot, float4* gbuf = nullptr) {
   const int lane = threadIdx.x & 63;
   const int by = tile_row(rowslot, F.grid_y);
   const int bx = tile_col(blockIdx.x, F.grid_x, 128 / (kTileW * 4));
@@ -463,11 +469,15 @@ __device__ __forceinline__ void pixel_body(const Frame& F, int rowslot) {
     f3 ro, rd;
     cast_ray(F, lane_uv(F, 0, px, -1), lane_uv(F, 1, py, -1), ro, rd);
     if (COUNT) c.rays++;
-    f3 col = render<COUNT, true>(F, ro, rd, c);
+    f3 col;
+    if constexpr (GBUF) col = render<COUNT, true>(F, ro, rd, c, GbufStore{gbuf + 2 * idx, true});
+    else col = render<COUNT, true>(F, ro, rd, c);
     o0 = col.x;
     o1 = col.y;
     o2 = col.z;
     o3 = 1.0f;
+  } else if (GBUF) {
+    gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
   }
   store_pixel(F, idx, o0, o1, o2, o3);
   if (COUNT) {
@@ -490,8 +500,10 @@ __device__ __forceinline__ void pixel_body(const Frame& F, int rowslot) {
 // s == 0 sums the samples in the reference's fixed order ((c0+c1)+c2)+c3 via
 // lane shuffles before the /4 (glsl:315-335).
 constexpr int kSampleTileW = 4, kSampleTileH = 4;
-template <bool COUNT>
-__device__ __forceinline__ void sample_body(const Frame& F, int rowslot) {
+// GBUF: lane s == 0 stores its own sample's hit, the pixel's rm_gbuffer_px
+// (k_gbuf_sample, rm_gbuffer.hip).
+template <bool COUNT, bool GBUF = false>
+__device__ __forceinline__ void sample_body(const Frame& F, int rowslot, float4* gbuf = nullptr) {
   const int lane = threadIdx.x & 63;
   const int s = lane & 3, q = lane >> 2;
   const int by = tile_row(rowslot, F.grid_y);
@@ -510,7 +522,8 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot) {
     f3 ro, rd;
     cast_ray(F, lane_uv(F, 0, px, s), lane_uv(F, 1, py, s), ro, rd);
     if (COUNT) c.rays++;
-    col = render<COUNT>(F, ro, rd, c);
+    if constexpr (GBUF) col = render<COUNT, false>(F, ro, rd, c, GbufStore{gbuf + 2 * idx, s == 0});
+    else col = render<COUNT>(F, ro, rd, c);
   }
 #ifdef RM_DPP_AA
   // the quad's other samples by DPP quad permutes (lane s = 0 reads lanes 1, 2, 3
@@ -555,6 +568,7 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot) {
     store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
   } else {
     store_pixel(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (GBUF) gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
   }
   if (COUNT) F.sdf_counts[idx] = cnt;
 }

@@ -998,4 +998,43 @@ __device__ __forceinline__ void store_pixel(const Frame& F, size_t idx, float r,
   if (F.rgba32f) reinterpret_cast<float4*>(F.rgba32f)[idx] = make_float4(r, g, b, a);
 }
 
+// ---- the primary hit's way out of render / trender (RM_OUT_GBUFFER) ----
+// render hands the hit it holds (t, id, the normal it has just computed, the
+// albedo) to a sink, once per ray, before it shades.  NoHit is every render
+// kernel's and every ray query's sink: nothing.  GbufStore writes the pixel's
+// rm_gbuffer_px at once (two 16-byte stores), so no field of the hit has to
+// stay live across the shading; `on` is false in the lanes of an AA pixel's
+// samples 1..3.
+struct NoHit {
+  __device__ __forceinline__ void operator()(float, int, f3, f3) const {}
+};
+// (the calls sit under `if constexpr (wants_hit<HIT>::value)`: with NoHit render is,
+// statement for statement, the function it was before it had a sink)
+template <class HIT>
+struct wants_hit {
+  static constexpr bool value = true;
+};
+template <>
+struct wants_hit<NoHit> {
+  static constexpr bool value = false;
+};
+struct GbufArgs {  // kernel argument beside the Frame
+  float4* px;      // [rows][width] rm_gbuffer_px, 2 x 16 B each
+};
+__device__ __forceinline__ void gbuf_store(float4* rec, float t, int id, f3 n, f3 a) {
+  rec[0] = make_float4(t, __int_as_float(id), n.x, n.y);
+  rec[1] = make_float4(n.z, a.x, a.y, a.z);
+}
+// The GLSL's dummy RayHit {-1, 0, -1, 1.0} (glsl:128), normal 0: a miss, and a shard's padding row.
+__device__ __forceinline__ void gbuf_store_miss(float4* rec) {
+  gbuf_store(rec, -1.0f, -1, mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f));
+}
+struct GbufStore {
+  float4* rec;
+  bool on;
+  __device__ __forceinline__ void operator()(float t, int id, f3 n, f3 a) const {
+    if (on) gbuf_store(rec, t, id, n, a);
+  }
+};
+
 }  // namespace rmd

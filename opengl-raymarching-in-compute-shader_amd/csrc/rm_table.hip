@@ -1262,9 +1262,10 @@ __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3
   return color;
 }
 
-// render glsl:218-251
-template <bool COUNT, int KL, int SL = 0>
-__device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd, TCnt& c) {
+// render glsl:218-251.  hit: where the primary hit goes besides (rm_scene.hpp NoHit /
+// GbufStore), called once: after the normal on a hit, after the march on a miss.
+template <bool COUNT, int KL, int SL = 0, class HIT = NoHit>
+__device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd, TCnt& c, HIT hit = HIT()) {
   f3 color = subs(mk(0.30f, 0.36f, 0.60f), rd.y * 0.2f);
   THit h = tmarch<COUNT, KL, SL>(S, ro, rd, false, c, F.prepv);
 #ifdef RM_TDBL_MARCH
@@ -1273,6 +1274,9 @@ __device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd,
     h.t = (h2.t == h.t) ? h.t : __builtin_nanf("");
   }
 #endif
+  if constexpr (wants_hit<HIT>::value) {
+    if (h.t == -1.0f) hit(h.t, h.id, mk(0.0f, 0.0f, 0.0f), h.color);  // tmarch's miss: id -1, colour 0
+  }
   if (h.t != -1.0f) {
     const f3 pos = add(ro, muls(rd, h.t));
     f3 normal = tnormal<COUNT>(S, pos, c, true, h.d);
@@ -1282,6 +1286,7 @@ __device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd,
       normal = mk(fminf(normal.x, n2.x), fminf(normal.y, n2.y), fminf(normal.z, n2.z));
     }
 #endif
+    if constexpr (wants_hit<HIT>::value) hit(h.t, h.id, normal, h.color);
     if (COUNT) c.lights++;
     color = point_light(F, h.color, normal, pos);
     if (h.id == 7) {
@@ -1387,8 +1392,10 @@ __device__ __forceinline__ size_t out_index(const Frame& F, int tx, int ty, int 
 }
 
 // main glsl:291-344 without AA: one lane per pixel, 8x8 pixels per wave.
-template <bool COUNT, int KL, int SL>
-__device__ __forceinline__ void table_pixel_body(const Frame& F, float* lds, int rowslot) {
+// GBUF: the pixel's rm_gbuffer_px goes to gbuf as well (k_table_gbuf_pixel,
+// rm_table_gbuffer.hip).
+template <bool COUNT, int KL, int SL, bool GBUF = false>
+__device__ __forceinline__ void table_pixel_body(const Frame& F, float* lds, int rowslot, float4* gbuf = nullptr) {
   const Table S = stage(F, lds);
   const int lane = threadIdx.x;
   const int by = tile_row(rowslot, gridDim.y);
@@ -1401,12 +1408,15 @@ __device__ __forceinline__ void table_pixel_body(const Frame& F, float* lds, int
   TCnt c = {0, 0, 0, 0, 0, 0};
   if (py < 0) {
     store_pixel(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (GBUF) gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
     return;
   }
   f3 ro, rd;
   cast_ray(F, lane_uv(F, 0, px, -1), lane_uv(F, 1, py, -1), ro, rd);
   if (COUNT) c.rays++;
-  const f3 col = trender<COUNT, KL, SL>(F, S, ro, rd, c);
+  f3 col;
+  if constexpr (GBUF) col = trender<COUNT, KL, SL>(F, S, ro, rd, c, GbufStore{gbuf + 2 * idx, true});
+  else col = trender<COUNT, KL, SL>(F, S, ro, rd, c);
   const size_t at = out_index(F, out_lane() & 7, out_lane() >> 3, 8, bx, by);
   store_pixel(F, at, col.x, col.y, col.z, 1.0f);
   if (COUNT) {
@@ -1418,8 +1428,10 @@ __device__ __forceinline__ void table_pixel_body(const Frame& F, float* lds, int
 // main glsl:291-344 with 4x supersampling: one lane per (pixel, sample), the 4
 // samples of a pixel in adjacent lanes, summed in the reference's order
 // ((c0 + c1) + c2) + c3 before the / 4 (glsl:315-335).
-template <bool COUNT, int KL, int SL>
-__device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, int rowslot) {
+// GBUF: lane s == 0 stores its own sample's hit, the pixel's rm_gbuffer_px
+// (k_table_gbuf_sample, rm_table_gbuffer.hip).
+template <bool COUNT, int KL, int SL, bool GBUF = false>
+__device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, int rowslot, float4* gbuf = nullptr) {
   const Table S = stage(F, lds);
   const int lane = threadIdx.x, s = lane & 3, q = lane >> 2;
   const int by = tile_row(rowslot, gridDim.y);
@@ -1434,7 +1446,11 @@ __device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, in
     f3 ro, rd;
     cast_ray(F, lane_uv(F, 0, px, s), lane_uv(F, 1, py, s), ro, rd);
     if (COUNT) c.rays++;
-    col = trender<COUNT, KL, SL>(F, S, ro, rd, c);
+    if constexpr (GBUF)
+      col = trender<COUNT, KL, SL>(F, S, ro, rd, c,
+                                   GbufStore{gbuf + 2 * ((size_t)lrow * (size_t)F.width + (size_t)px), s == 0});
+    else
+      col = trender<COUNT, KL, SL>(F, S, ro, rd, c);
   }
   const float r1 = __shfl(col.x, lane + 1), g1 = __shfl(col.y, lane + 1), b1 = __shfl(col.z, lane + 1);
   const float r2 = __shfl(col.x, lane + 2), g2 = __shfl(col.y, lane + 2), b2 = __shfl(col.z, lane + 2);
@@ -1456,6 +1472,7 @@ __device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, in
     store_pixel(F, at, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
   } else {
     store_pixel(F, at, 0.0f, 0.0f, 0.0f, 0.0f);
+    if (GBUF) gbuf_store_miss(gbuf + 2 * at);  // a shard's padding row
   }
   if (COUNT) F.sdf_counts[at] = cnt;
 }

@@ -38,6 +38,8 @@ RM_CONFIG_MAGIC = 0x36434D52
 RM_MAX_BATCH = 32
 RM_OUT_RGBA8 = 1
 RM_OUT_RGBA32F = 2
+RM_OUT_GBUFFER = 4  # every pixel's primary hit, rm_gbuffer_px (Renderer.read_gbuffer)
+RM_HAS_GBUFFER = 1
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -128,6 +130,16 @@ class rm_ray_hit(C.Structure):
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("id", "<i4"), ("material", "<f4"), ("albedo", "<f4", (3,)),
                           ("normal", "<f4", (3,)), ("color", "<f4", (3,))])
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(rm_ray_hit) == 48
+
+
+class rm_gbuffer_px(C.Structure):
+    _fields_ = [("t", C.c_float), ("id", C.c_int32), ("normal", C.c_float * 3), ("albedo", C.c_float * 3)]
+
+
+# rm_gbuffer_px as a numpy record (Renderer.read_gbuffer's pixels): rm_ray_hit's fields of
+# the same names, with the same miss values
+GBUFFER_DTYPE = np.dtype([("t", "<f4"), ("id", "<i4"), ("normal", "<f4", (3,)), ("albedo", "<f4", (3,))])
+assert GBUFFER_DTYPE.itemsize == C.sizeof(rm_gbuffer_px) == 32
 
 
 # runtime scene table (include/rm_api.h)
@@ -262,6 +274,9 @@ _SIGS = {
     "rm_trace_rays": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
     "rm_trace_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
     "rm_pick": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(rm_ray_hit)]),
+    "rm_read_gbuffer": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
+    "rm_set_output_gbuffer": (C.c_int, [_P, _P]),
+    "rm_get_output_gbuffer": (C.c_int, [_P, C.POINTER(_P)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -594,6 +609,14 @@ class Renderer:
         _check(lib().rm_read_rgba32f(self._h, out.ctypes.data, 0, int(flip_y)), self._h)
         return out
 
+    def read_gbuffer(self, flip_y: bool = False) -> np.ndarray:
+        """The last dispatch's G-buffer (RM_OUT_GBUFFER, rm_read_gbuffer): a [rows, width]
+        GBUFFER_DTYPE array, one primary hit per pixel (t, id, normal, albedo; a miss is
+        t = -1, id = -1, the rest 0).  With AA on it is the first sample's ray."""
+        out = np.empty((self.rows, self.width), GBUFFER_DTYPE)
+        _check(lib().rm_read_gbuffer(self._h, out.ctypes.data, 0, int(flip_y)), self._h)
+        return out
+
     def counters(self) -> dict:
         c = rm_counters()
         _check(lib().rm_get_counters(self._h, C.byref(c)), self._h)
@@ -654,6 +677,16 @@ class Renderer:
     def output_rgba8_ptr(self) -> int:
         p = C.c_void_p()
         _check(lib().rm_get_output_rgba8(self._h, C.byref(p)), self._h)
+        return p.value or 0
+
+    def set_output_gbuffer(self, device_ptr: Optional[int]) -> None:
+        """Render the G-buffer into a caller-owned device buffer of rows * width * 32 bytes,
+        16-byte aligned; None restores the context's own (rm_set_output_gbuffer)."""
+        _check(lib().rm_set_output_gbuffer(self._h, device_ptr), self._h)
+
+    def output_gbuffer_ptr(self) -> int:
+        p = C.c_void_p()
+        _check(lib().rm_get_output_gbuffer(self._h, C.byref(p)), self._h)
         return p.value or 0
 
     def wait_output(self, stream_ptr: Optional[int]) -> None:
