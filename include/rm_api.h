@@ -440,6 +440,75 @@ int rm_trace_rays_device(rm_ctx *ctx, const void *origins_dev, const void *dirs_
  * the bottom row: a window cursor's y maps to height - 1 - y. */
 int rm_pick(rm_ctx *ctx, int32_t px, int32_t py, rm_ray_hit *hit);
 
+/* ---- SDF field queries: distance, id and normal at points and on grids ---------
+ * A ray query cannot return a distance at a point.  These calls evaluate the
+ * scene's sdf() (glsl:107-123) and GetNormal() (glsl:278-288) themselves: keep a
+ * camera or a particle set out of the objects, bake the scene into a 3-D
+ * distance volume for meshing, a physics broad phase or another renderer's 3-D
+ * texture.
+ *
+ * Points: point i is points[i], [n][3] floats; its answer is one rm_ray_hit.
+ *  - t is sdf(p).hitpoint: the GLSL's sdf() returns a RayHit whose hitpoint is
+ *    the distance (negative inside an object).  id, material and albedo are the
+ *    opU winner's (albedo is checkers(p) for a checkers entry); normal is
+ *    GetNormal(p) under RM_SDF_NORMAL, else 0; color is always 0.  There is no
+ *    miss record: sdf() always has a winner.  A NaN distance loses every <, so
+ *    the last entry wins.
+ * Grids: point (i, j, k) has the coordinate origin[a] + (float)idx * step[a] on
+ * each axis a: one IEEE multiply, then one IEEE add, no FMA.
+ *  - The outputs are dist[nz][ny][nx] float and ids[nz][ny][nx] int32
+ *    (RayHit.id), x fastest.  Either pointer may be NULL, not both.  Device
+ *    pointers need 4-byte alignment only (16-byte stores are used where the
+ *    pointers and nx allow).  Every dim is in 0..2^24 and their product at most
+ *    2^31 - 1; a zero dim (the others valid) is RM_OK, writes nothing and looks at
+ *    no pointer, as n == 0 does for points.  origin and step may be
+ *    any floats: zero, negative, infinite or NaN.
+ *
+ *  - A query uses the context's current uniforms and scene at the time of the
+ *    call; of the uniforms only iTime is read (it drives the blend).  The
+ *    uniforms are checked as rm_set_uniforms checks them.  The scene is the
+ *    built-in one or the rm_set_scene table (a context with rm_scene_specialize
+ *    on queries with the generic table code).
+ *  - Every input, of any value, gives the reference's result: -0, huge, infinite
+ *    and NaN coordinates included.
+ *  - Queries are ordered on the context's stream (rm_set_stream's when one is
+ *    set) after the work already queued.  They touch neither the context's
+ *    images nor its G-buffer nor its counters nor its batch ring, and are not
+ *    part of graph replay.  A context with cfg.counters queries with the
+ *    production device code and leaves rm_counters alone.  With rm_enable_timing
+ *    on, a query's launch is bracketed and counted like a trace launch.
+ *  - The points of one wave are 64 consecutive indices: a caller that wants speed
+ *    keeps neighbouring points neighbouring; any order is correct.
+ *  - A sharded context, or one of an rm_comm_init communicator, evaluates
+ *    locally: the call is not collective.  A multi-device context
+ *    (cfg.ngpus >= 1): RM_ERR_STATE.  G-buffer contexts are allowed.
+ *
+ * Returns: n == 0 is RM_OK and writes nothing.  RM_ERR_INVALID for a null
+ * pointer with work to do, n < 0 or n > 2^31 - 1, unknown flag bits, an out_dev
+ * that is not 16-byte aligned, a grid with both outputs NULL, a dim that is
+ * negative or above 2^24, a product above 2^31 - 1, a grid output that is not
+ * 4-byte aligned.  A null context: RM_ERR_INVALID, nothing touched. */
+#define RM_HAS_SDF_QUERY 1
+/* rm_sdf flags */
+#define RM_SDF_VALUE  0   /* sdf(p) glsl:107-123: t = RayHit.hitpoint (the distance, negative inside), id, material, albedo */
+#define RM_SDF_NORMAL 2   /* + GetNormal(p) glsl:278-288 (same bit as RM_TRACE_NORMAL) */
+
+/* Host points and records; synchronous (upload, evaluate, download through
+ * staging buffers the context owns, grown on demand, freed by rm_destroy). */
+int rm_sdf_points(rm_ctx *ctx, const float *points, int64_t n, uint32_t flags, rm_ray_hit *out);
+/* Device pointers; asynchronous on the context's stream.  out_dev: 16-byte aligned. */
+int rm_sdf_points_device(rm_ctx *ctx, const void *points_dev, int64_t n, uint32_t flags, void *out_dev);
+
+typedef struct rm_sdf_grid_desc {  /* 36 bytes; x, y, z */
+  float   origin[3];
+  float   step[3];
+  int32_t dims[3];
+} rm_sdf_grid_desc;
+/* Host outputs; synchronous. */
+int rm_sdf_grid(rm_ctx *ctx, const rm_sdf_grid_desc *grid, float *dist, int32_t *ids);
+/* Device outputs; asynchronous on the context's stream. */
+int rm_sdf_grid_device(rm_ctx *ctx, const rm_sdf_grid_desc *grid, void *dist_dev, void *ids_dev);
+
 /* ---- G-buffer: every pixel's primary hit, from the frame kernels themselves ----
  * The reference's author wanted a normal and a depth view of the frame (both
  * commented out in render(), glsl:229, 248-249).  With RM_OUT_GBUFFER in

@@ -186,11 +186,13 @@ void free_all(rm_ctx* c) {
   c->comm = nullptr;
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
-                   (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits}) {
+                   (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits,
+                   &c->d_sdf_in, &c->d_sdf_out}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   c->trace_cap = 0;
+  c->sdf_in_cap = c->sdf_out_cap = 0;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);
   for (float* p : c->ring32) (void)hipFree(p);

@@ -1,7 +1,8 @@
 // rm_ctx.hpp — the context, and what the files of librm's C-ABI share:
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
-// rm_api_trace.hip (ray queries) and rm_api_gbuffer.hip (the G-buffer image).
+// rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image) and
+// rm_api_sdf.hip (SDF field queries).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -15,6 +16,7 @@
 #include "rm_internal.hpp"
 #include "rm_jit.hpp"
 #include "rm_scene.hpp"
+#include "rm_sdf_args.hpp"
 
 static_assert(RM_MAX_BATCH == rmd::kMaxBatch, "rm_api.h RM_MAX_BATCH == rm_scene.hpp kMaxBatch");
 
@@ -35,6 +37,14 @@ hipError_t launch_trace(const rmd::Frame& F, const void* origins, const void* di
                         uint32_t flags, hipStream_t s);
 hipError_t launch_table_trace(const rmd::Frame& F, const void* origins, const void* dirs, void* hits,
                               int64_t n, uint32_t flags, hipStream_t s);
+// SDF field queries (rm_sdf.hip, rm_table_sdf.hip): n >= 1 points, a grid of dims >= 1
+// (rm_sdf_args.hpp SdfGridArgs), device pointers
+hipError_t launch_sdf_points(const rmd::Frame& F, const void* points, void* out, int64_t n, uint32_t flags,
+                             hipStream_t s);
+hipError_t launch_table_sdf_points(const rmd::Frame& F, const void* points, void* out, int64_t n, uint32_t flags,
+                                   hipStream_t s);
+hipError_t launch_sdf_grid(const rmd::Frame& F, const rmd::SdfGridArgs& G, hipStream_t s);
+hipError_t launch_table_sdf_grid(const rmd::Frame& F, const rmd::SdfGridArgs& G, hipStream_t s);
 // the frame kernels with the G-buffer output (rm_gbuffer.hip, rm_table_gbuffer.hip):
 // gbuf is a 16-byte aligned device pointer to F.rows * F.width rm_gbuffer_px
 hipError_t launch_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
@@ -154,6 +164,11 @@ struct rm_ctx {
   float* d_trace_rays = nullptr;
   void* d_trace_hits = nullptr;
   int64_t trace_cap = 0;
+  // rm_sdf_points' / rm_sdf_grid's staging buffers, grown on demand (bytes): the points, or a
+  // grid's ids; the records, or a grid's distances
+  void* d_sdf_in = nullptr;
+  void* d_sdf_out = nullptr;
+  size_t sdf_in_cap = 0, sdf_out_cap = 0;
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;

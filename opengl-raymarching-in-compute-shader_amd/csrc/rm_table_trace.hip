@@ -10,23 +10,9 @@
 #include "rm_table.hip"
 
 #include "rm_trace.hpp"
+#include "rm_table_lit.hpp"
 
 namespace rmd {
-
-// The table for the literal path: every entry at every point, opU in table
-// order (Table::dist_mask over all entries; prim_dist's full-range form is the
-// GLSL's operations over the whole float range already).
-struct TableLit {
-  const Table& S;
-  __device__ __forceinline__ float dist(f3 p, int& k) const {
-    return S.dist_mask(p, S.n >= 32 ? 0xffffffffu : (1u << S.n) - 1u, k);
-  }
-  __device__ __forceinline__ void attrs(int k, f3 p, int& id, float& material, f3& color) const {
-    id = S.id(k);
-    material = S.material(k);
-    color = S.color(k, p);
-  }
-};
 
 // As k_trace (rm_trace.hip), over the staged table.  One instance serves every
 // table: EX_MAX_SLOTS lazy slots hold any table's, and TLazy is the march every

@@ -14,49 +14,7 @@
 
 namespace rmd {
 
-// The built-in scene (glsl:107-123) for the literal path: every primitive, every
-// operation as the GLSL writes it.  scene_exact (rm_scene.hpp) is the same sdf for
-// finite points only: its v_min / v_max drop a NaN operand, its plane is p.y + 5.5
-// (the dot product's x * 0 and z * 0 are NaN for an infinite p) and sqrt_core
-// takes finite sums.
-struct BuiltinLit {
-  float blend, omblend;
-  __device__ __forceinline__ float dist(f3 p, int& id) const {
-    auto opu = [&](float d, float v, int k) {  // opU glsl:105: (d1 < d2) ? d1 : d2
-      const bool keep = d < v;
-      id = keep ? id : k;
-      return keep ? d : v;
-    };
-    id = 0;
-    float d = lit_len(sub(p, mk(15.0f, 0.0f, -10.0f))) - 3.0f;                    // glsl:111
-    d = opu(d, lit_len(sub(p, mk(-25.0f, 0.0f, -10.0f))) - 3.0f, 1);              // glsl:112
-    {                                                                              // glsl:115-117
-      const f3 q = sub(p, mk(-5.0f, 0.0f, -10.0f));
-      const f3 e = mk(fabsf(q.x) - 3.0f, fabsf(q.y) - 2.5f, fabsf(q.z) - 2.5f);
-      const float box = gmin(gmax(e.x, gmax(e.y, e.z)), 0.0f) +
-                        lit_len(mk(gmax(e.x, 0.0f), gmax(e.y, 0.0f), gmax(e.z, 0.0f)));
-      const float sph = lit_len(q) - 3.0f;
-      d = opu(d, box * omblend + sph * blend, 4);
-    }
-    {                                                                              // glsl:119
-      const f3 q = sub(p, mk(-5.0f, 0.0f, 10.0f));  // sdTorus(q.xzy, (2.5, 0.5))
-      const float l = lit_sqrt(q.x * q.x + q.y * q.y) - 2.5f;
-      d = opu(d, lit_sqrt(l * l + q.z * q.z) - 0.5f, 5);
-    }
-    {                                                                              // glsl:120
-      const f3 pa = sub(sub(p, mk(-5.0f, -2.0f, -30.0f)), mk(CAP_AX, CAP_AY, CAP_AZ));
-      const f3 ba = mk(CAP_BAX, CAP_BAY, CAP_BAZ);
-      const float h = gmin(gmax(dot(pa, ba) / dot(ba, ba), 0.0f), 1.0f);
-      d = opu(d, lit_len(sub(pa, muls(ba, h))) - 1.0f, 6);
-    }
-    return opu(d, dot(p, mk(0.0f, 1.0f, 0.0f)) + 5.5f, 7);                         // glsl:85,121
-  }
-  __device__ __forceinline__ void attrs(int k, f3 p, int& id, float& material, f3& color) const {
-    id = k;
-    material = k == 7 ? 0.0f : 1.0f;  // MATTE: the floor alone
-    color = hit_color(k, p);
-  }
-};
+// (BuiltinLit, the built-in scene of the literal path: rm_trace.hpp)
 
 // One ray per lane, 64 consecutive rays per one-wave workgroup; the flags are
 // uniform.  The query Frame has prepv[PREP_VALID] = 0 and unit_rd = 0

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 from typing import Optional, Sequence
 
 import numpy as np
@@ -54,6 +55,10 @@ RM_TRACE_REFLECTED = 1  # reflectedRay's limits instead (256 steps, tmax 200)
 RM_TRACE_NORMAL = 2     # + GetNormal(ro + rd t) on a hit
 RM_TRACE_SHADE = 4      # + render(ro, rd): the colour a pixel sample with this ray gets
 RM_TRACE_SHADOW = 8     # alone: t = softshadow(ro, rd, k)
+# SDF field queries (rm_sdf_points, rm_sdf_grid): flags
+RM_HAS_SDF_QUERY = 1
+RM_SDF_VALUE = 0        # sdf(p): t = the distance (negative inside), id, material, albedo
+RM_SDF_NORMAL = 2       # + GetNormal(p) (the same bit as RM_TRACE_NORMAL)
 
 
 class RMError(RuntimeError):
@@ -130,6 +135,13 @@ class rm_ray_hit(C.Structure):
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("id", "<i4"), ("material", "<f4"), ("albedo", "<f4", (3,)),
                           ("normal", "<f4", (3,)), ("color", "<f4", (3,))])
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(rm_ray_hit) == 48
+
+
+class rm_sdf_grid_desc(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("step", C.c_float * 3), ("dims", C.c_int32 * 3)]  # x, y, z
+
+
+assert C.sizeof(rm_sdf_grid_desc) == 36
 
 
 class rm_gbuffer_px(C.Structure):
@@ -274,6 +286,10 @@ _SIGS = {
     "rm_trace_rays": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
     "rm_trace_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P]),
     "rm_pick": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(rm_ray_hit)]),
+    "rm_sdf_points": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P]),
+    "rm_sdf_points_device": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P]),
+    "rm_sdf_grid": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), _P, _P]),
+    "rm_sdf_grid_device": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), _P, _P]),
     "rm_read_gbuffer": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "rm_set_output_gbuffer": (C.c_int, [_P, _P]),
     "rm_get_output_gbuffer": (C.c_int, [_P, C.POINTER(_P)]),
@@ -473,6 +489,13 @@ class Renderer:
         self.rank0_rows = rank0_rows
         self.shard_format = shard_format
         self.ngpus = ngpus
+        # the context's device ordinal; -1 (the device current at creation) is resolved here,
+        # once, with torch where it is loaded: librm and torch share one HIP runtime (lib())
+        self.device = device
+        if device < 0 and "torch" in sys.modules:
+            import torch
+            if torch.cuda.is_available():
+                self.device = torch.cuda.current_device()
         self.rows = (shard_rows(height, row_block, nshards, shard, rank0_rows)[1]
                      if nshards > 1 and not ngpus else height)
 
@@ -666,6 +689,61 @@ class Renderer:
         _check(lib().rm_pick(self._h, int(px), int(py),
                              C.cast(hit.ctypes.data, C.POINTER(rm_ray_hit))), self._h)
         return hit[0]
+
+    # -- SDF field queries (rm_sdf_points, rm_sdf_grid)
+    def sdf(self, points, flags: int = RM_SDF_VALUE):
+        """sdf(p), and under RM_SDF_NORMAL GetNormal(p), at points of the scene with the
+        current uniforms: one rm_ray_hit per point, `t` the distance (negative inside).
+
+        A numpy (n, 3) float32 array: synchronous, returns a RAY_HIT_DTYPE array of n records
+        (rm_sdf_points).  A torch device tensor, (n, 3) float32 contiguous: asynchronous on the
+        context's stream (set_stream), returns an (n, 12) float32 device tensor holding the
+        records, `id` as its bits (rm_sdf_points_device; no copy is made)."""
+        if not isinstance(points, np.ndarray) and hasattr(points, "data_ptr"):
+            import torch
+            if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()
+                    and points.dim() == 2 and points.shape[1] == 3):
+                raise ValueError("sdf: device points must be a contiguous (n, 3) float32 tensor")
+            n = int(points.shape[0])
+            out = torch.empty((n, 12), dtype=torch.float32, device=points.device)
+            _check(lib().rm_sdf_points_device(self._h, points.data_ptr(), n, int(flags), out.data_ptr()),
+                   self._h)
+            return out
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("sdf: points must be (n, 3)")
+        out = np.empty(p.shape[0], RAY_HIT_DTYPE)
+        _check(lib().rm_sdf_points(self._h, p.ctypes.data, p.shape[0], int(flags), out.ctypes.data), self._h)
+        return out
+
+    def sdf_grid(self, origin, step, dims, ids: bool = False, device: bool = False):
+        """The scene's distance on a regular grid (rm_sdf_grid): point (i, j, k) is
+        origin + (i, j, k) * step per axis (one float32 multiply, then one add); dims is
+        (nx, ny, nz).  Returns `dist`, float32 of shape (nz, ny, nx), or with ids=True the
+        pair (dist, ids), ids int32 (RayHit.id) of the same shape.  device=True: torch tensors
+        on the context's device, asynchronous on its stream (rm_sdf_grid_device)."""
+        nx, ny, nz = (int(d) for d in dims)
+        if min(nx, ny, nz) < 0:
+            raise ValueError("sdf_grid: dims must not be negative")
+        g = rm_sdf_grid_desc((C.c_float * 3)(*[float(v) for v in origin]),
+                             (C.c_float * 3)(*[float(v) for v in step]), (C.c_int32 * 3)(nx, ny, nz))
+        if device:
+            import torch
+            if self.device < 0:
+                raise RuntimeError("sdf_grid: device=True needs torch loaded when the context was created")
+            dev = torch.device("cuda", self.device)
+            dist = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+            idt = torch.empty((nz, ny, nx), dtype=torch.int32, device=dev) if ids else None
+            if min(nx, ny, nz) == 0:  # nothing to write: the empty tensors (their data_ptr is 0)
+                return (dist, idt) if ids else dist
+            _check(lib().rm_sdf_grid_device(self._h, C.byref(g), dist.data_ptr(),
+                                            idt.data_ptr() if ids else None), self._h)
+        else:
+            dist = np.empty((nz, ny, nx), np.float32)
+            idt = np.empty((nz, ny, nx), np.int32) if ids else None
+            _check(lib().rm_sdf_grid(self._h, C.byref(g), dist.ctypes.data,
+                                     idt.ctypes.data if ids else None), self._h)
+        return (dist, idt) if ids else dist
 
     # -- device interop
     def set_stream(self, stream_ptr: Optional[int]) -> None:
