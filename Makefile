@@ -27,9 +27,10 @@ RM_SRCS  := $(CSRC)/rm_api.hip $(CSRC)/rm_api_comm.hip $(CSRC)/rm_api_graph.hip 
             $(CSRC)/rm_kernels.hip $(CSRC)/rm_table.hip $(CSRC)/rm_jit.hip $(CSRC)/rm_host.cpp $(CSRC)/rm_comm.cpp \
             $(CSRC)/rm_api_trace.hip $(CSRC)/rm_trace.hip $(CSRC)/rm_table_trace.hip \
             $(CSRC)/rm_api_gbuffer.hip $(CSRC)/rm_gbuffer.hip $(CSRC)/rm_table_gbuffer.hip \
-            $(CSRC)/rm_api_sdf.hip $(CSRC)/rm_sdf.hip $(CSRC)/rm_table_sdf.hip
+            $(CSRC)/rm_api_sdf.hip $(CSRC)/rm_sdf.hip $(CSRC)/rm_table_sdf.hip \
+            $(CSRC)/rm_api_adaptive.hip $(CSRC)/rm_adaptive.hip $(CSRC)/rm_table_adaptive.hip
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
-            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp \
+            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp \
             include/rm_api.h Makefile
 # The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
 # the names they #include each other by.
@@ -109,6 +110,17 @@ $(PKG)/build/rm_table_sdf.o: $(CSRC)/rm_table_sdf.hip $(CSRC)/rm_table.hip $(RM_
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
 
+# The adaptive-supersampling kernels (rm_dispatch_adaptive / rm_dispatch_refine,
+# DESIGN §4.12), in objects of their own in the same way: rm_adaptive.o with
+# rm_gbuffer.o's flags, rm_table_adaptive.o with rm_table_gbuffer.o's.
+$(PKG)/build/rm_adaptive.o: $(CSRC)/rm_adaptive.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(KFLAGS) -c $< -o $@
+
+$(PKG)/build/rm_table_adaptive.o: $(CSRC)/rm_table_adaptive.hip $(CSRC)/rm_table.hip $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
+
 $(PKG)/build/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
 	@mkdir -p $(dir $@)
 	python3 $(PKG)/tools/embed_sources.py $@ $(JIT_SRCS)
@@ -130,7 +142,8 @@ $(LIBRM): $(PKG)/build/rm_api.o $(PKG)/build/rm_api_comm.o $(PKG)/build/rm_api_g
           $(PKG)/build/rm_kernels.o $(PKG)/build/rm_kernels_aa.o $(PKG)/build/rm_table.o $(PKG)/build/rm_jit.o $(PKG)/build/rm_host.o $(PKG)/build/rm_comm.o \
           $(PKG)/build/rm_api_trace.o $(PKG)/build/rm_trace.o $(PKG)/build/rm_table_trace.o \
           $(PKG)/build/rm_api_gbuffer.o $(PKG)/build/rm_gbuffer.o $(PKG)/build/rm_table_gbuffer.o \
-          $(PKG)/build/rm_api_sdf.o $(PKG)/build/rm_sdf.o $(PKG)/build/rm_table_sdf.o
+          $(PKG)/build/rm_api_sdf.o $(PKG)/build/rm_sdf.o $(PKG)/build/rm_table_sdf.o \
+          $(PKG)/build/rm_api_adaptive.o $(PKG)/build/rm_adaptive.o $(PKG)/build/rm_table_adaptive.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
@@ -204,7 +217,8 @@ SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-fra
 ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_frame_math.o rm_kernels.o rm_kernels_aa.o rm_table.o rm_jit.o rm_host.o rm_comm.o \
                                       rm_api_trace.o rm_trace.o rm_table_trace.o \
                                       rm_api_gbuffer.o rm_gbuffer.o rm_table_gbuffer.o \
-                                      rm_api_sdf.o rm_sdf.o rm_table_sdf.o)
+                                      rm_api_sdf.o rm_sdf.o rm_table_sdf.o \
+                                      rm_api_adaptive.o rm_adaptive.o rm_table_adaptive.o)
 asan: $(ASANLIB) $(ASANORC)
 
 $(ASAN_DIR)/rm_trace.o: $(CSRC)/rm_kernels.hip
@@ -213,6 +227,8 @@ $(ASAN_DIR)/rm_gbuffer.o: $(CSRC)/rm_kernels.hip
 $(ASAN_DIR)/rm_table_gbuffer.o: $(CSRC)/rm_table.hip
 $(ASAN_DIR)/rm_sdf.o: $(CSRC)/rm_kernels.hip
 $(ASAN_DIR)/rm_table_sdf.o: $(CSRC)/rm_table.hip
+$(ASAN_DIR)/rm_adaptive.o: $(CSRC)/rm_kernels.hip
+$(ASAN_DIR)/rm_table_adaptive.o: $(CSRC)/rm_table.hip
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(RM_HDRS) $(PKG)/build/rm_jit_src.inc
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -I$(PKG)/build -c $< -o $@

@@ -66,6 +66,8 @@ inline int dispatchCompute(rm_ctx* p) { return rm_dispatch(p); }
 inline int dispatchFrames(rm_ctx* p, const rm_uniforms* frames, int n) {
   return rm_dispatch_frames(p, frames, n);
 }
+// the AA-off frame, 4x supersampled only where it has edges (rm_dispatch_adaptive)
+inline int dispatchAdaptive(rm_ctx* p, int threshold = 8) { return rm_dispatch_adaptive(p, threshold); }
 inline int memoryBarrier(rm_ctx* p) { return rm_synchronize(p); }
 
 }  // namespace rm

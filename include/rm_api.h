@@ -559,6 +559,67 @@ int rm_read_gbuffer(rm_ctx *ctx, rm_gbuffer_px *dst, size_t row_pitch, int flip_
 int rm_set_output_gbuffer(rm_ctx *ctx, void *device_ptr);
 int rm_get_output_gbuffer(rm_ctx *ctx, void **device_ptr);
 
+/* ---- adaptive supersampling: 4 samples only where the frame has edges -----------
+ * An extension, like RM_SHADOW_HARD.  The frame of these calls is the AA-off
+ * frame with every FLAGGED pixel replaced by that pixel of the AA-on frame, so
+ * every pixel is exactly one of two reference values.
+ *
+ *  - Pass 1: every pixel is what rm_dispatch with AA = 0 writes (the centre ray,
+ *    glsl:301-305).
+ *  - Flagging, rm_dispatch_adaptive: pixel p is flagged iff some 4-neighbour q
+ *    (left, right, below, above) inside the frame has
+ *    max over R, G, B of |p_c - q_c| > threshold, on the RGBA8 values of pass 1
+ *    (round(clamp(c, 0, 1) * 255), NaN -> 0: what rm_read_rgba8 returns; a context
+ *    with only RM_OUT_RGBA32F quantises the same floats the same way).  Alpha
+ *    takes no part.  Threshold 255 flags nothing (the frame is the AA-off frame);
+ *    a 1x1 frame has no neighbour and flags nothing.
+ *  - Flagging, rm_dispatch_refine / _device: the caller's mask, [height][width]
+ *    bytes, row 0 the bottom row, rows row_pitch bytes apart (0 = width); any
+ *    non-zero byte flags its pixel (foveation, a G-buffer criterion of the
+ *    caller's own, a previous frame's mask).  The context keeps its own
+ *    normalised 0/1 copy, which rm_read_aa_mask and rm_get_aa_mask return; the
+ *    device mask may be that copy itself (row_pitch 0 or width).
+ *  - Refinement: a flagged pixel gets the reference's four cumulative sample rays
+ *    (glsl:309-336), summed ((c0 + c1) + c2) + c3, then / 4: the AA-on frame's
+ *    pixel bit for bit in RGBA32F and byte for byte in RGBA8.
+ *  - The reference's AA samples sit at +0.125 .. +1 pixel from the pixel's centre
+ *    ray, not around it: a refined pixel is the reference's AA pixel with that
+ *    shift.  These calls do not re-centre it.
+ *  - u.AA is ignored and the context's uniforms stay as they are; bounceVar,
+ *    shadow_mode, iTime, the light and the camera apply as in rm_dispatch.
+ *  - Afterwards the context reads as after an rm_dispatch (rm_read_rgba8 /
+ *    _rgba32f, rm_get_output_rgba8, rm_set_output_rgba8, rm_wait_output,
+ *    rm_synchronize).  Nothing is sticky: the next rm_dispatch or
+ *    rm_dispatch_frames is what it always was.  Everything is queued on the
+ *    context's stream (rm_set_stream's when one is set); with rm_enable_timing
+ *    one event pair brackets the whole sequence, one launch of one frame.
+ *  - This version: one-device, whole-frame contexts; the built-in scene and
+ *    rm_set_scene tables (with rm_scene_specialize on, pass 1 uses the kernel
+ *    rm_dispatch would, the refinement the generic table code, as ray queries do:
+ *    same values); colour contrast is the only built-in criterion.  RM_ERR_STATE
+ *    on a context with counters, nshards > 1, a communicator, ngpus >= 1,
+ *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay.
+ *  - The environment variable RM_AA_REFINE_WAVES (1..65535, read by rm_create)
+ *    overrides the refinement's grid size, min(ceil(W H / 16), 128 x compute units)
+ *    one-wave workgroups. */
+#define RM_HAS_ADAPTIVE_AA 1
+
+/* threshold in 0..255 (else RM_ERR_INVALID).  Asynchronous. */
+int rm_dispatch_adaptive(rm_ctx *ctx, int32_t threshold);
+/* A host mask: uploaded synchronously (the caller's buffer is free on return),
+ * the frame itself is asynchronous.  RM_ERR_INVALID for a null mask or a
+ * row_pitch below width. */
+int rm_dispatch_refine(rm_ctx *ctx, const uint8_t *mask, size_t row_pitch);
+/* A device mask, read on the context's stream.  Asynchronous. */
+int rm_dispatch_refine_device(rm_ctx *ctx, const void *mask_dev, size_t row_pitch);
+/* Synchronous readback of the 0/1 mask of the last such dispatch; row_pitch
+ * (bytes, 0 = width) and flip_y as rm_read_rgba8.  RM_ERR_STATE before the first. */
+int rm_read_aa_mask(rm_ctx *ctx, uint8_t *dst, size_t row_pitch, int flip_y);
+/* The context's mask image, [height][width] uint8, tight (allocated on first use). */
+int rm_get_aa_mask(rm_ctx *ctx, void **device_ptr);
+/* Flagged pixels of the last such dispatch; synchronises.  RM_ERR_STATE before the first. */
+int rm_aa_refined(rm_ctx *ctx, int64_t *pixels);
+
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process
  * per GPU (torch.distributed.run, MPI).  Rank 0 creates an id and broadcasts it

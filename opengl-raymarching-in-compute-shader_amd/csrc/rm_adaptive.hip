@@ -1,0 +1,265 @@
+// rm_adaptive.hip — adaptive supersampling for the built-in scene, and its
+// bookkeeping for every scene (rm_dispatch_adaptive / rm_dispatch_refine,
+// include/rm_api.h).
+//
+// A translation unit of its own, so that the render kernels' code objects
+// (rm_kernels.o, rm_kernels_aa.o) are what they were without it.  The device
+// code is rm_kernels.hip's, included with both of its *_ONLY switches set, as
+// rm_gbuffer.hip includes it.
+//
+// The frame is k_pixel's (one centre ray per pixel, launched by the host as
+// pass 1) with the flagged pixels rendered again as k_sample renders them.  Four
+// kernels join the two:
+//   k_adapt_classify / k_adapt_mask
+//                      one wave per 8x8 tile (four per workgroup): the pixel's flag
+//                      (colour contrast against its 4-neighbours, or the caller's mask)
+//                      into the context's 0/1 mask, the tile's count by ballot + popcount;
+//   k_adapt_scan       exclusive scan of the tile counts, and their total;
+//   k_adapt_scatter    the flagged pixels' coordinates into a list, a tile's at its
+//                      offset in lane order (v_mbcnt): deterministic, an edge's pixels
+//                      adjacent, and no atomic anywhere;
+//   k_adapt_refine     16 list entries x 4 samples per wave and round: cast_ray,
+//                      render<>, the three-shuffle sum and store_pixel of k_sample's
+//                      sample_body, the same instantiations in the same order, so a
+//                      refined pixel is the AA-on frame's bit for bit.
+// This version: whole-frame, one-device contexts; no counting build.
+#define RM_KERNELS_PIXEL_ONLY
+#define RM_KERNELS_AA_ONLY
+#include "rm_kernels.hip"
+
+#include "rm_adaptive_args.hpp"
+
+namespace rmd {
+
+// One wave per 8x8 tile, four tiles of a tile row per workgroup: a grid of 4K's
+// 130 k one-wave workgroups costs such short kernels more to launch than to run.
+constexpr int kAdaptWaves = 4;
+
+// The wave's tile column (the tile row is blockIdx.y); the last workgroup of a row
+// may hold waves past tiles_x, whose lanes are all outside the frame.
+__device__ __forceinline__ int adapt_tx() { return blockIdx.x * kAdaptWaves + (int)(threadIdx.x >> 6); }
+
+// The lane's pixel of its wave's tile; false outside the frame.
+__device__ __forceinline__ bool adapt_pixel(const AdaptArgs& A, int& px, int& py) {
+  const int lane = threadIdx.x & 63;
+  px = adapt_tx() * kAdaptTile + (lane & 7);
+  py = blockIdx.y * kAdaptTile + (lane >> 3);
+  return px < A.width && py < A.height;
+}
+
+// The flag into the context's mask, the tile's count into counts (every lane of
+// the wave calls it: the ballot is over the whole tile).
+__device__ __forceinline__ void adapt_flag(const AdaptArgs& A, bool in, int px, int py, bool flag) {
+  if (in) A.mask[(size_t)py * (size_t)A.width + (size_t)px] = flag ? 1 : 0;
+  const unsigned long long m = __ballot(in && flag);
+  if ((threadIdx.x & 63) == 0 && adapt_tx() < A.tiles_x)
+    A.counts[(size_t)blockIdx.y * (size_t)A.tiles_x + adapt_tx()] = (uint8_t)__popcll(m);
+}
+
+// max over R, G, B of |p_c - q_c| > thr on RGBA8 words (alpha takes no part)
+__device__ __forceinline__ bool adapt_differs(uint32_t p, uint32_t q, int thr) {
+  bool f = false;
+#pragma unroll
+  for (int sh = 0; sh < 24; sh += 8) {
+    const int d = (int)((p >> sh) & 255u) - (int)((q >> sh) & 255u);
+    f = f | ((d < 0 ? -d : d) > thr);
+  }
+  return f;
+}
+
+// Pass 1's pixel as its RGBA8 word: the RGBA8 image's, or the RGBA32F image's
+// floats quantised as store_pixel quantises them.
+__device__ __forceinline__ uint32_t adapt_word(const uint32_t* rgba8, const float4* rgba32f, size_t i) {
+  if (rgba8) return rgba8[i];
+  const float4 v = rgba32f[i];
+  return quantize(v.x) | (quantize(v.y) << 8) | (quantize(v.z) << 16);
+}
+
+__global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_classify(AdaptArgs A, const uint32_t* __restrict__ rgba8,
+                                                       const float4* __restrict__ rgba32f, int thr) {
+  int px, py;
+  const bool in = adapt_pixel(A, px, py);
+  bool flag = false;
+  if (in) {
+    const size_t w = (size_t)A.width, i = (size_t)py * w + (size_t)px;
+    const uint32_t p = adapt_word(rgba8, rgba32f, i);
+    if (px > 0) flag |= adapt_differs(p, adapt_word(rgba8, rgba32f, i - 1), thr);
+    if (px + 1 < A.width) flag |= adapt_differs(p, adapt_word(rgba8, rgba32f, i + 1), thr);
+    if (py > 0) flag |= adapt_differs(p, adapt_word(rgba8, rgba32f, i - w), thr);
+    if (py + 1 < A.height) flag |= adapt_differs(p, adapt_word(rgba8, rgba32f, i + w), thr);
+  }
+  adapt_flag(A, in, px, py, flag);
+}
+
+// The caller's mask, rows `pitch` bytes apart: any non-zero byte flags its pixel.
+// src may be A.mask itself (pitch == width): a lane reads its byte before it writes it.
+__global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_mask(AdaptArgs A, const uint8_t* src, size_t pitch) {
+  int px, py;
+  const bool in = adapt_pixel(A, px, py);
+  const bool flag = in && src[(size_t)py * pitch + (size_t)px] != 0;
+  adapt_flag(A, in, px, py, flag);
+}
+
+// Exclusive scan of counts[0 .. nchunks * kAdaptScanChunk) into offsets, the sum
+// into *total: one workgroup, a chunk per round, 16 adjacent counts (one 16-byte
+// load) per lane.  The tail of the last chunk holds zeros (rm_adaptive_args.hpp).
+// Offsets are words: an exclusive offset is below width * height <= 2^32 for
+// every real tile; the total, which may be 2^32, is kept in 64 bits.
+__global__ __launch_bounds__(kAdaptScanLanes) void k_adapt_scan(const uint8_t* __restrict__ counts,
+                                                                uint32_t* __restrict__ offsets,
+                                                                unsigned long long* __restrict__ total,
+                                                                uint32_t nchunks) {
+  constexpr int kWaves = kAdaptScanLanes / 64;
+  __shared__ uint32_t wsum[kWaves];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  unsigned long long base = 0;  // everything before this chunk (uniform)
+  for (uint32_t ch = 0; ch < nchunks; ++ch) {
+    const size_t i0 = ((size_t)ch * kAdaptScanLanes + (size_t)t) * kAdaptScanPer;
+    const uint4 v = *reinterpret_cast<const uint4*>(counts + i0);
+    const uint32_t words[4] = {v.x, v.y, v.z, v.w};
+    uint32_t c[kAdaptScanPer], sum = 0;
+#pragma unroll
+    for (int j = 0; j < kAdaptScanPer; ++j) {
+      c[j] = (words[j >> 2] >> (8 * (j & 3))) & 255u;
+      sum += c[j];
+    }
+    uint32_t inc = sum;  // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t o = __shfl_up(inc, d);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+      const uint32_t s = wsum[k];
+      before += k < w ? s : 0u;
+      all += s;
+    }
+    __syncthreads();  // wsum is rewritten next round
+    uint32_t run = (uint32_t)base + before + (inc - sum);
+    uint32_t o[kAdaptScanPer];
+#pragma unroll
+    for (int j = 0; j < kAdaptScanPer; ++j) {
+      o[j] = run;
+      run += c[j];
+    }
+    uint4* dst = reinterpret_cast<uint4*>(offsets + i0);
+#pragma unroll
+    for (int j = 0; j < kAdaptScanPer / 4; ++j) dst[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+    base += all;
+  }
+  if (t == 0) *total = base;
+}
+
+// Lanes of the wave below this one that are set in m (v_mbcnt).
+__device__ __forceinline__ uint32_t adapt_prefix(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+__global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_scatter(AdaptArgs A) {
+  int px, py;
+  const bool in = adapt_pixel(A, px, py);
+  const bool flag = in && A.mask[(size_t)py * (size_t)A.width + (size_t)px] != 0;
+  const unsigned long long m = __ballot(flag);
+  if (!flag) return;
+  // (a flagged lane is inside the frame: its wave's tile is a real one)
+  const size_t at = (size_t)A.offsets[(size_t)blockIdx.y * (size_t)A.tiles_x + adapt_tx()] + adapt_prefix(m);
+  A.list[at] = (uint32_t)px | ((uint32_t)py << 16);  // both <= 65535
+}
+
+// The lane id re-formed after the march (rm_table.hip out_lane): the list entry is
+// read again from it instead of px, py staying live across render<>.
+__device__ __forceinline__ int adapt_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// The frame constants as k_sample_frames takes them (a batch of one): a round
+// reads the fields it needs from the kernel arguments at an index the compiler
+// cannot see through, as that kernel reads its frame's, so they are scalar loads
+// where they are used instead of some 80 SGPRs live around the whole loop (which
+// spilled: 52 SGPRs and 13 VGPRs, 56 B of scratch per lane).
+struct AdaptFrame {
+  Frame f[1];
+};
+
+// Waves per SIMD the register allocation must allow: k_sample's.
+__global__ __launch_bounds__(64, 8) void k_adapt_refine(AdaptFrame B, AdaptArgs A) {
+  // the host does not know the count: every wave reads it (a uniform load) and
+  // strides over the groups of 16 entries by the grid
+  const unsigned long long total = *A.total;
+  const unsigned long long ngroups = (total + 15ull) >> 4;
+  for (unsigned long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    int slot = 0;
+    asm volatile("" : "+s"(slot));
+    const Frame& F = B.f[slot];
+    // the group's entries: 16, or what is left of the list (indices below 2^32)
+    const uint32_t* __restrict__ ent = A.list + g * 16ull;
+    const unsigned long long left = total - g * 16ull;
+    const int n = left < 16ull ? (int)left : 16;
+    // entry q = lane >> 2 of the group, sample s = lane & 3: as sample_body's lanes.
+    // The spare lanes of a partial last group stay idle (all 4 of a pixel together).
+    f3 col = mk(0.0f, 0.0f, 0.0f);
+    {
+      const int lane = threadIdx.x & 63;
+      if ((lane >> 2) < n) {
+        const uint32_t e = ent[lane >> 2];
+        Cnt c = {0, 0, 0, 0, 0, 0};
+        f3 ro, rd;
+        cast_ray(F, lane_uv(F, 0, (int)(e & 0xffffu), lane & 3), lane_uv(F, 1, (int)(e >> 16), lane & 3), ro, rd);
+        col = render<false>(F, ro, rd, c);
+      }
+    }
+    const int ol = adapt_lane();
+    const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
+    const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
+    const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+    if ((ol & 3) == 0 && (ol >> 2) < n) {
+      const uint32_t e = ent[ol >> 2];
+      const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
+      const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3, o2 = ((col.z + b1) + b2) + b3;
+      store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+    }
+  }
+}
+
+}  // namespace rmd
+
+namespace rm {
+
+// mask_src: the caller's device mask at mask_pitch (k_adapt_mask), or null: colour
+// contrast above `threshold` on pass 1's image, F.rgba8 or else F.rgba32f
+// (k_adapt_classify).  Then the scan and the scatter.  A's counts and offsets hold
+// whole scan chunks (rm_adaptive_args.hpp).
+hipError_t launch_adapt_flags(const rmd::Frame& F, const rmd::AdaptArgs& A, const void* mask_src, size_t mask_pitch,
+                              int threshold, hipStream_t s) {
+  const unsigned tiles_y = (unsigned)((A.height + rmd::kAdaptTile - 1) / rmd::kAdaptTile);
+  const dim3 tiles((unsigned)((A.tiles_x + rmd::kAdaptWaves - 1) / rmd::kAdaptWaves), tiles_y), wg(64 * rmd::kAdaptWaves);
+  if (mask_src)
+    hipLaunchKernelGGL(rmd::k_adapt_mask, tiles, wg, 0, s, A, static_cast<const uint8_t*>(mask_src), mask_pitch);
+  else
+    hipLaunchKernelGGL(rmd::k_adapt_classify, tiles, wg, 0, s, A, reinterpret_cast<const uint32_t*>(F.rgba8),
+                       reinterpret_cast<const float4*>(F.rgba32f), threshold);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const size_t ntiles = (size_t)A.tiles_x * tiles_y;
+  const uint32_t nchunks = (uint32_t)((ntiles + rmd::kAdaptScanChunk - 1) / rmd::kAdaptScanChunk);
+  hipLaunchKernelGGL(rmd::k_adapt_scan, dim3(1), dim3(rmd::kAdaptScanLanes), 0, s, A.counts, A.offsets, A.total, nchunks);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(rmd::k_adapt_scatter, tiles, wg, 0, s, A);
+  return hipGetLastError();
+}
+
+// The listed pixels of frame F of the built-in scene, on `waves` one-wave workgroups.
+hipError_t launch_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s) {
+  rmd::AdaptFrame B;
+  B.f[0] = F;
+  hipLaunchKernelGGL(rmd::k_adapt_refine, dim3((unsigned)waves), dim3(64), 0, s, B, A);
+  return hipGetLastError();
+}
+
+}  // namespace rm

@@ -1,0 +1,28 @@
+// rm_adaptive_args.hpp — the kernel arguments of adaptive supersampling
+// (rm_dispatch_adaptive / rm_dispatch_refine), shared by the
+// kernels (rm_adaptive.hip, rm_table_adaptive.hip) and the host (rm_api_adaptive.hip).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace rmd {
+
+// Tiles are 8x8 pixels, one wave each, numbered row-major: tile = ty * tiles_x + tx.
+constexpr int kAdaptTile = 8;
+// k_adapt_scan takes the tile counts in chunks of this many (1024 lanes x 16
+// counts); the counts and offsets are allocated, and the counts zeroed, up to a
+// whole number of chunks, so the scan needs no bounds.
+constexpr int kAdaptScanLanes = 1024, kAdaptScanPer = 16;
+constexpr size_t kAdaptScanChunk = (size_t)kAdaptScanLanes * kAdaptScanPer;
+
+struct AdaptArgs {
+  uint8_t* mask;              // [height][width], 0 / 1: the context's copy
+  uint8_t* counts;            // [tiles] flagged pixels of a tile, 0..64
+  uint32_t* offsets;          // [tiles] exclusive scan of counts
+  unsigned long long* total;  // [1] all flagged pixels (up to 2^32: one more than a word holds)
+  uint32_t* list;             // [total] px | py << 16, tile by tile, a tile's in lane order
+  int32_t width, height, tiles_x;
+};
+
+}  // namespace rmd

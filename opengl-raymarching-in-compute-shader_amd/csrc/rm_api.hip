@@ -187,12 +187,14 @@ void free_all(rm_ctx* c) {
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
                    (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits,
-                   &c->d_sdf_in, &c->d_sdf_out}) {
+                   &c->d_sdf_in, &c->d_sdf_out, (void**)&c->d_aa_mask, (void**)&c->d_aa_list, (void**)&c->d_aa_counts,
+                   (void**)&c->d_aa_offsets, (void**)&c->d_aa_total}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   c->trace_cap = 0;
   c->sdf_in_cap = c->sdf_out_cap = 0;
+  c->aa_dispatched = false;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);
   for (float* p : c->ring32) (void)hipFree(p);
@@ -320,6 +322,11 @@ int rm_create(rm_ctx** out, const rm_config* cfg) {
     c->cfg.nshards = 1;
     c->cfg.shard = 0;
     if (c->cfg.row_block <= 0) c->cfg.row_block = 1;
+  }
+  // the grid of adaptive supersampling's refinement (rm_api_adaptive.hip), when set
+  if (const char* v = std::getenv("RM_AA_REFINE_WAVES")) {
+    const long n = std::strtol(v, nullptr, 10);
+    if (n >= 1 && n <= 65535) c->aa_waves_env = (int)n;
   }
   c->rgb3 = c->cfg.nshards > 1 && c->cfg.shard_format == RM_SHARD_RGB8 && (c->cfg.outputs & RM_OUT_RGBA8);
   if (cfg->device >= 0) {

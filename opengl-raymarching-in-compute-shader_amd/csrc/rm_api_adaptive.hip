@@ -1,0 +1,206 @@
+// rm_api_adaptive.hip — librm's C-ABI for adaptive supersampling (include/rm_api.h
+// RM_HAS_ADAPTIVE_AA): rm_dispatch_adaptive, rm_dispatch_refine /
+// _device, and the mask and the count of the last such dispatch.
+//
+// One such dispatch is, on the context's stream: pass 1 (the kernel rm_dispatch
+// would launch for the frame with AA off), the flags (rm_adaptive.hip: colour
+// contrast on pass 1's image, or the caller's mask), their scan and list, and the
+// refinement of the listed pixels (rm_adaptive.hip for the built-in scene,
+// rm_table_adaptive.hip for a table).  The host never learns the count.
+//
+// This version: one-device, whole-frame contexts.  Out of scope, and refused:
+// sharded, communicator and multi-device contexts (a pixel's neighbour may live
+// on another rank), G-buffer contexts, counting contexts, batches and graph
+// replay; hiprtc-specialised refine kernels (the generic table code refines);
+// any built-in criterion other than colour contrast.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+
+#include "rm_ctx.hpp"
+
+using namespace rm;
+
+namespace {
+
+size_t adapt_tiles(const rm_ctx* c) {
+  const size_t t = rmd::kAdaptTile;
+  return ((c->cfg.width + t - 1) / t) * ((c->cfg.height + t - 1) / t);
+}
+
+// RM_ERR_STATE for the contexts this version does not serve, naming the call.
+int refuse(rm_ctx* c, const char* call) {
+  const std::string who = std::string(call) + ": ";
+  if (!c->subs.empty() || c->cfg.ngpus >= 1)
+    return fail(c, RM_ERR_STATE, who + "not available on a multi-GPU context (rm_config.ngpus)");
+  if (c->comm || c->group_member || c->comm_failed)
+    return fail(c, RM_ERR_STATE, who + "not available on a communicator context (rm_comm_init)");
+  if (c->cfg.nshards > 1) return fail(c, RM_ERR_STATE, who + "not available on a sharded context (nshards > 1)");
+  if (c->cfg.counters) return fail(c, RM_ERR_STATE, who + "not available with counters");
+  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, who + "not available on a G-buffer context (RM_OUT_GBUFFER)");
+  if (c->graph_on) return fail(c, RM_ERR_STATE, who + "not available with rm_graph_enable on");
+  return RM_OK;
+}
+
+// The context's buffers, on first use; kept until rm_destroy.
+int ensure_buffers(rm_ctx* c) {
+  if (c->d_aa_total) return RM_OK;
+  const size_t npx = (size_t)c->cfg.width * (size_t)c->cfg.height;
+  const size_t padded = (adapt_tiles(c) + rmd::kAdaptScanChunk - 1) / rmd::kAdaptScanChunk * rmd::kAdaptScanChunk;
+  if (!c->d_aa_mask) RM_HIP(c, hipMalloc(&c->d_aa_mask, npx));
+  if (!c->d_aa_list) RM_HIP(c, hipMalloc(&c->d_aa_list, npx * sizeof(uint32_t)));
+  if (!c->d_aa_offsets) RM_HIP(c, hipMalloc(&c->d_aa_offsets, padded * sizeof(uint32_t)));
+  if (!c->d_aa_counts) {
+    RM_HIP(c, hipMalloc(&c->d_aa_counts, padded));
+    // the tail of the last scan chunk stays zero: no kernel writes it
+    RM_HIP(c, hipMemsetAsync(c->d_aa_counts, 0, padded, c->stream));
+    RM_HIP(c, hipStreamSynchronize(c->stream));  // once: a later rm_set_stream need not order it
+  }
+  if (!c->aa_cus) {
+    int cus = 0;
+    RM_HIP(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    c->aa_cus = cus > 0 ? cus : 1;
+  }
+  RM_HIP(c, hipMalloc(&c->d_aa_total, sizeof(unsigned long long)));  // last: marks the set complete
+  return RM_OK;
+}
+
+// The refinement's grid: the host does not know the count, so a fixed number of
+// one-wave workgroups stride over the groups.  Four times the waves the device
+// holds at k_adapt_refine's 8 per SIMD (32 per compute unit), or as many as the
+// frame has groups: the hardware hands the queued waves to the SIMDs as they
+// free up, which balances the groups' very uneven costs better than 32 per unit
+// striding further each (4K cfg3 frames at threshold 8, alone on the device:
+// 1.04 ms at 32 per unit, 0.99 at 64, 0.85 at 128, 0.86 at 65535 waves;
+// profiles/adaptive_probe.txt).
+constexpr size_t kRefineWavesPerCU = 128;
+int refine_waves(const rm_ctx* c) {
+  if (c->aa_waves_env) return c->aa_waves_env;
+  const size_t groups = ((size_t)c->cfg.width * (size_t)c->cfg.height + 15) / 16;
+  return (int)std::min(groups, (size_t)c->aa_cus * kRefineWavesPerCU);
+}
+
+// One adaptive frame.  mask_src: a device mask at mask_pitch, or null for the
+// colour-contrast flags at `threshold`.
+int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int threshold) {
+  int rc;
+  if ((rc = order_after_batch(c)) != RM_OK) return rc;
+  rmd::Frame F = make_frame(c);
+  F.aa = 0;  // pass 1 is the AA-off frame whatever u.AA says; the uniforms stay
+  rm::pixel_grid(F.width, F.rows, false, &F.grid_x, &F.grid_y);
+  rmd::AdaptArgs A;
+  A.mask = c->d_aa_mask;
+  A.counts = c->d_aa_counts;
+  A.offsets = c->d_aa_offsets;
+  A.total = c->d_aa_total;
+  A.list = c->d_aa_list;
+  A.width = c->cfg.width;
+  A.height = c->cfg.height;
+  A.tiles_x = (c->cfg.width + rmd::kAdaptTile - 1) / rmd::kAdaptTile;
+  hipEvent_t e0, e1;
+  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
+  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  if ((rc = phase(c, 0)) != RM_OK) return rc;
+  hipError_t e = launch(pick_kernel(c, F), F, false, c->stream);
+  if (e != hipSuccess) return hip_fail(c, e, "adaptive pass 1 launch");
+  if ((e = launch_adapt_flags(F, A, mask_src, mask_pitch, threshold, c->stream)) != hipSuccess)
+    return hip_fail(c, e, "adaptive flag launch");
+  e = c->nprims ? launch_table_adapt_refine(F, A, refine_waves(c), c->stream)
+                : launch_adapt_refine(F, A, refine_waves(c), c->stream);
+  if (e != hipSuccess) return hip_fail(c, e, "adaptive refine launch");
+  if ((rc = phase(c, 1)) != RM_OK) return rc;
+  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
+  if (c->timing) {
+    c->ph_recorded = true;
+    c->ph_comm = false;
+  }
+  c->dispatched = true;
+  c->aa_dispatched = true;
+  return RM_OK;
+}
+
+// What every such dispatch checks and prepares before its frame.
+int begin(rm_ctx* c, const char* call) {
+  int rc = refuse(c, call);
+  if (rc != RM_OK) return rc;
+  if ((rc = check_uniforms(c, c->u)) != RM_OK) return rc;
+  if ((rc = set_device(c)) != RM_OK) return rc;
+  return ensure_buffers(c);
+}
+
+int check_mask(rm_ctx* c, const char* call, const void* mask, size_t* row_pitch) {
+  if (!mask) return fail(c, RM_ERR_INVALID, std::string(call) + ": null mask");
+  if (*row_pitch == 0) *row_pitch = (size_t)c->cfg.width;
+  if (*row_pitch < (size_t)c->cfg.width)
+    return fail(c, RM_ERR_INVALID, std::string(call) + ": row_pitch smaller than a row");
+  return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_dispatch_adaptive(rm_ctx* c, int32_t threshold) {
+  if (!c) return RM_ERR_INVALID;
+  if (threshold < 0 || threshold > 255)
+    return fail(c, RM_ERR_INVALID, "rm_dispatch_adaptive: threshold must be in 0..255");
+  const int rc = begin(c, "rm_dispatch_adaptive");
+  if (rc != RM_OK) return rc;
+  return adaptive_frame(c, nullptr, 0, threshold);
+}
+
+int rm_dispatch_refine(rm_ctx* c, const uint8_t* mask, size_t row_pitch) {
+  if (!c) return RM_ERR_INVALID;
+  int rc = check_mask(c, "rm_dispatch_refine", mask, &row_pitch);
+  if (rc != RM_OK) return rc;
+  if ((rc = begin(c, "rm_dispatch_refine")) != RM_OK) return rc;
+  // into the context's mask, tight, behind whatever still reads it; the caller's
+  // buffer is free on return.  k_adapt_mask then normalises it in place.
+  const size_t w = (size_t)c->cfg.width;
+  RM_HIP(c, hipMemcpy2DAsync(c->d_aa_mask, w, mask, row_pitch, w, (size_t)c->cfg.height, hipMemcpyHostToDevice,
+                             c->stream));
+  RM_HIP(c, hipStreamSynchronize(c->stream));
+  return adaptive_frame(c, c->d_aa_mask, w, 0);
+}
+
+int rm_dispatch_refine_device(rm_ctx* c, const void* mask_dev, size_t row_pitch) {
+  if (!c) return RM_ERR_INVALID;
+  int rc = check_mask(c, "rm_dispatch_refine_device", mask_dev, &row_pitch);
+  if (rc != RM_OK) return rc;
+  if ((rc = begin(c, "rm_dispatch_refine_device")) != RM_OK) return rc;
+  return adaptive_frame(c, mask_dev, row_pitch, 0);
+}
+
+int rm_read_aa_mask(rm_ctx* c, uint8_t* dst, size_t row_pitch, int flip_y) {
+  if (!c) return RM_ERR_INVALID;
+  if (!c->aa_dispatched)
+    return fail(c, RM_ERR_STATE, "rm_read_aa_mask: no rm_dispatch_adaptive / rm_dispatch_refine yet");
+  return read_image(c, c->d_aa_mask, 1, dst, row_pitch, flip_y);
+}
+
+int rm_get_aa_mask(rm_ctx* c, void** device_ptr) {
+  if (!c || !device_ptr) return RM_ERR_INVALID;
+  int rc = refuse(c, "rm_get_aa_mask");
+  if (rc != RM_OK) return rc;
+  if ((rc = set_device(c)) != RM_OK) return rc;
+  if ((rc = ensure_buffers(c)) != RM_OK) return rc;
+  *device_ptr = c->d_aa_mask;
+  return RM_OK;
+}
+
+int rm_aa_refined(rm_ctx* c, int64_t* pixels) {
+  if (!c || !pixels) return RM_ERR_INVALID;
+  if (!c->aa_dispatched)
+    return fail(c, RM_ERR_STATE, "rm_aa_refined: no rm_dispatch_adaptive / rm_dispatch_refine yet");
+  const int rc = set_device(c);
+  if (rc != RM_OK) return rc;
+  unsigned long long n = 0;
+  RM_HIP(c, hipStreamSynchronize(c->stream));
+  RM_HIP(c, hipMemcpy(&n, c->d_aa_total, sizeof n, hipMemcpyDeviceToHost));
+  *pixels = (int64_t)n;
+  return RM_OK;
+}
+
+}  // extern "C"

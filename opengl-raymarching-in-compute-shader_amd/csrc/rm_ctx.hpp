@@ -1,8 +1,8 @@
 // rm_ctx.hpp — the context, and what the files of librm's C-ABI share:
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
-// rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image) and
-// rm_api_sdf.hip (SDF field queries).
+// rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
+// rm_api_sdf.hip (SDF field queries) and rm_api_adaptive.hip (adaptive supersampling).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "rm_adaptive_args.hpp"
 #include "rm_comm.hpp"
 #include "rm_internal.hpp"
 #include "rm_jit.hpp"
@@ -49,6 +50,13 @@ hipError_t launch_table_sdf_grid(const rmd::Frame& F, const rmd::SdfGridArgs& G,
 // gbuf is a 16-byte aligned device pointer to F.rows * F.width rm_gbuffer_px
 hipError_t launch_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
 hipError_t launch_table_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
+// adaptive supersampling (rm_adaptive.hip, rm_table_adaptive.hip): the flags of pass 1's
+// image F.rgba8 / F.rgba32f (mask_src null) or of a device mask, scanned and listed; then
+// the listed pixels rendered as the AA-on frame's, on `waves` one-wave workgroups
+hipError_t launch_adapt_flags(const rmd::Frame& F, const rmd::AdaptArgs& A, const void* mask_src, size_t mask_pitch,
+                              int threshold, hipStream_t s);
+hipError_t launch_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
+hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
 
 // Which kernel renders a frame (rm_api.hip pick_kernel): the built-in scene's, or
 // for a runtime scene table its specialised kernels (jit) or the generic table
@@ -169,6 +177,17 @@ struct rm_ctx {
   void* d_sdf_in = nullptr;
   void* d_sdf_out = nullptr;
   size_t sdf_in_cap = 0, sdf_out_cap = 0;
+  // adaptive supersampling (rm_api_adaptive.hip), allocated on first use: the 0/1 mask
+  // [height][width], the flagged pixels' list [height * width], the 8x8 tiles' counts and
+  // offsets (whole scan chunks, rm_adaptive_args.hpp) and the total
+  uint8_t* d_aa_mask = nullptr;
+  uint32_t* d_aa_list = nullptr;
+  uint8_t* d_aa_counts = nullptr;
+  uint32_t* d_aa_offsets = nullptr;
+  unsigned long long* d_aa_total = nullptr;
+  bool aa_dispatched = false;  // the mask and the total are those of a dispatch
+  int aa_waves_env = 0;        // RM_AA_REFINE_WAVES at rm_create (0: unset)
+  int aa_cus = 0;              // the device's compute units (first adaptive dispatch)
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;

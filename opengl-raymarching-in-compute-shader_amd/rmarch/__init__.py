@@ -41,6 +41,7 @@ RM_OUT_RGBA8 = 1
 RM_OUT_RGBA32F = 2
 RM_OUT_GBUFFER = 4  # every pixel's primary hit, rm_gbuffer_px (Renderer.read_gbuffer)
 RM_HAS_GBUFFER = 1
+RM_HAS_ADAPTIVE_AA = 1  # Renderer.dispatch_adaptive / dispatch_refine
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -293,6 +294,12 @@ _SIGS = {
     "rm_read_gbuffer": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "rm_set_output_gbuffer": (C.c_int, [_P, _P]),
     "rm_get_output_gbuffer": (C.c_int, [_P, C.POINTER(_P)]),
+    "rm_dispatch_adaptive": (C.c_int, [_P, C.c_int32]),
+    "rm_dispatch_refine": (C.c_int, [_P, _P, C.c_size_t]),
+    "rm_dispatch_refine_device": (C.c_int, [_P, _P, C.c_size_t]),
+    "rm_read_aa_mask": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
+    "rm_get_aa_mask": (C.c_int, [_P, C.POINTER(_P)]),
+    "rm_aa_refined": (C.c_int, [_P, C.POINTER(C.c_int64)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -597,6 +604,52 @@ class Renderer:
         n = len(frames)
         arr = (rm_uniforms * n)(*frames)
         _check(lib().rm_dispatch_frames(self._h, arr, n), self._h)
+
+    # -- adaptive supersampling (rm_dispatch_adaptive, rm_dispatch_refine)
+    def dispatch_adaptive(self, u: Optional[rm_uniforms] = None, threshold: int = 8) -> None:
+        """The AA-off frame with 4x supersampling only where it has edges
+        (rm_dispatch_adaptive): a pixel whose RGBA8 colour differs from a 4-neighbour's by
+        more than `threshold` (0..255) in R, G or B becomes the AA-on frame's pixel, bit for
+        bit.  u.AA is ignored.  Asynchronous; reads back like dispatch()."""
+        if u is not None:
+            self.set_uniforms(u)
+        _check(lib().rm_dispatch_adaptive(self._h, int(threshold)), self._h)
+
+    def dispatch_refine(self, mask, u: Optional[rm_uniforms] = None, row_pitch: int = 0) -> None:
+        """The same with the caller's flags (rm_dispatch_refine): `mask` is a numpy
+        (height, width) array, row 0 the bottom row, any non-zero byte flags its pixel
+        (uploaded synchronously); or an int, a device pointer to such bytes, rows
+        `row_pitch` bytes apart (0 = width), read on the context's stream
+        (rm_dispatch_refine_device)."""
+        if u is not None:
+            self.set_uniforms(u)
+        if isinstance(mask, np.ndarray):
+            m = mask if mask.dtype == np.uint8 else (mask != 0).astype(np.uint8)
+            if m.ndim != 2 or m.shape != (self.height, self.width):
+                raise ValueError("dispatch_refine: mask must be (height, width)")
+            if m.strides[1] != 1 or m.strides[0] < self.width:
+                m = np.ascontiguousarray(m)
+            _check(lib().rm_dispatch_refine(self._h, m.ctypes.data, m.strides[0]), self._h)
+        else:
+            _check(lib().rm_dispatch_refine_device(self._h, mask, int(row_pitch)), self._h)
+
+    def read_aa_mask(self, flip_y: bool = False) -> np.ndarray:
+        """The 0/1 mask, (height, width) uint8, of the last dispatch_adaptive / dispatch_refine."""
+        out = np.empty((self.height, self.width), np.uint8)
+        _check(lib().rm_read_aa_mask(self._h, out.ctypes.data, 0, int(flip_y)), self._h)
+        return out
+
+    def aa_mask_ptr(self) -> int:
+        """The context's mask image on the device, [height][width] uint8 (rm_get_aa_mask)."""
+        p = C.c_void_p()
+        _check(lib().rm_get_aa_mask(self._h, C.byref(p)), self._h)
+        return p.value or 0
+
+    def aa_refined(self) -> int:
+        """Flagged pixels of the last dispatch_adaptive / dispatch_refine; synchronises."""
+        n = C.c_int64(0)
+        _check(lib().rm_aa_refined(self._h, C.byref(n)), self._h)
+        return int(n.value)
 
     def read_frame_rgba8(self, k: int, flip_y: bool = False) -> np.ndarray:
         out = np.empty((self.rows, self.width, 4), np.uint8)
