@@ -68,6 +68,13 @@ inline int dispatchFrames(rm_ctx* p, const rm_uniforms* frames, int n) {
 }
 // the AA-off frame, 4x supersampled only where it has edges (rm_dispatch_adaptive)
 inline int dispatchAdaptive(rm_ctx* p, int threshold = 8) { return rm_dispatch_adaptive(p, threshold); }
+// the same, flagged by geometric edges of pass 1's G-buffer (rm_dispatch_adaptive_edges;
+// RM_OUT_GBUFFER): ids, depths and normals at the defaults of rm_aa_criteria_init
+inline int dispatchAdaptiveEdges(rm_ctx* p, const rm_aa_criteria* criteria = nullptr) {
+  rm_aa_criteria c;
+  if (!criteria) rm_aa_criteria_init(&c);
+  return rm_dispatch_adaptive_edges(p, criteria ? criteria : &c);
+}
 inline int memoryBarrier(rm_ctx* p) { return rm_synchronize(p); }
 
 }  // namespace rm

@@ -596,9 +596,11 @@ int rm_get_output_gbuffer(rm_ctx *ctx, void **device_ptr);
  *  - This version: one-device, whole-frame contexts; the built-in scene and
  *    rm_set_scene tables (with rm_scene_specialize on, pass 1 uses the kernel
  *    rm_dispatch would, the refinement the generic table code, as ray queries do:
- *    same values); colour contrast is the only built-in criterion.  RM_ERR_STATE
- *    on a context with counters, nshards > 1, a communicator, ngpus >= 1,
- *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay.
+ *    same values); colour contrast is the only built-in criterion of
+ *    rm_dispatch_adaptive (rm_dispatch_adaptive_edges below has the geometric
+ *    ones).  RM_ERR_STATE on a context with counters, nshards > 1, a
+ *    communicator, ngpus >= 1, RM_OUT_GBUFFER or rm_graph_enable on; no batches,
+ *    no graph replay.
  *  - The environment variable RM_AA_REFINE_WAVES (1..65535, read by rm_create)
  *    overrides the refinement's grid size, min(ceil(W H / 16), 128 x compute units)
  *    one-wave workgroups. */
@@ -619,6 +621,79 @@ int rm_read_aa_mask(rm_ctx *ctx, uint8_t *dst, size_t row_pitch, int flip_y);
 int rm_get_aa_mask(rm_ctx *ctx, void **device_ptr);
 /* Flagged pixels of the last such dispatch; synchronises.  RM_ERR_STATE before the first. */
 int rm_aa_refined(rm_ctx *ctx, int64_t *pixels);
+
+/* ---- adaptive supersampling by geometric edges, from pass 1's own G-buffer ------
+ * rm_dispatch_adaptive_edges is rm_dispatch_adaptive with another flagging step:
+ * pass 1, the refinement and everything under "Afterwards" above are the same,
+ * and the frame is again the AA-off frame with every flagged pixel replaced by
+ * the AA-on frame's.  The flags are the union of the criteria selected in
+ * rm_aa_criteria.edges, evaluated on the device on what pass 1 has just written:
+ * its rm_gbuffer_px records (the G-buffer section above) and / or its RGBA8 image.
+ *
+ *  - Flagging: pixel p is flagged iff some 4-neighbour q (left, right, below,
+ *    above) inside the frame satisfies at least one selected criterion for the
+ *    pair (p, q):
+ *      RM_AA_EDGE_COLOR   max over R, G, B of |p_c - q_c| > color_threshold on pass
+ *                         1's RGBA8 values: rm_dispatch_adaptive's rule, word for word;
+ *      RM_AA_EDGE_ID      p.id != q.id (a miss has id -1, so a hit beside a miss is
+ *                         an edge and two misses are not);
+ *      RM_AA_EDGE_DEPTH   both hit and fabsf(p.t - q.t) > depth_rel * fminf(p.t, q.t);
+ *      RM_AA_EDGE_NORMAL  both hit and
+ *                         (p.normal[0] * q.normal[0] + p.normal[1] * q.normal[1])
+ *                           + p.normal[2] * q.normal[2] < normal_cos;
+ *      RM_AA_EDGE_ALBEDO  p.albedo[c] != q.albedo[c] for some c (the floor's checker
+ *                         edges, and every edge between two colours).
+ *    p and q are pass 1's records: the centre ray's hit, the ray rm_pick casts.
+ *    "Hit" is t != -1.0f, the GLSL's own test.  Every float operation is one IEEE
+ *    single-precision operation in the order written, no FMA: three separate
+ *    multiplies and two separate adds in the dot product.  The compares are the
+ *    ones written, so a NaN fails > and < and passes !=: a NaN normal is no
+ *    NORMAL edge, a NaN albedo is an ALBEDO edge, a NaN t is a hit and no DEPTH
+ *    edge.  Every pair test is symmetric in p and q, so the mask is symmetric
+ *    like the colour rule's: if q flags p, p flags q.  A 1x1 frame flags nothing.
+ *    depth_rel = +inf under DEPTH alone flags nothing (a hit has t >= 0, so
+ *    the right-hand side is +inf, or NaN at t = 0); depth_rel = 0 flags
+ *    every pair of hits with different t.
+ *  - Contexts: ID, DEPTH, NORMAL and ALBEDO read the G-buffer and need
+ *    RM_OUT_GBUFFER in rm_config.outputs; without it RM_ERR_STATE.  COLOR alone
+ *    works wherever rm_dispatch_adaptive does, and on G-buffer contexts too.  A
+ *    context with RM_OUT_GBUFFER and no colour output has nothing to refine:
+ *    RM_ERR_STATE.  Otherwise as rm_dispatch_adaptive: RM_ERR_STATE with
+ *    counters, nshards > 1, a communicator, ngpus >= 1 or rm_graph_enable on;
+ *    the built-in scene and rm_set_scene tables.  rm_dispatch_adaptive,
+ *    rm_dispatch_refine and rm_dispatch_refine_device keep refusing G-buffer
+ *    contexts; rm_read_aa_mask, rm_get_aa_mask and rm_aa_refined serve them.
+ *  - The G-buffer afterwards: rm_read_gbuffer, and the buffer of
+ *    rm_set_output_gbuffer (the one classified, when one is set), hold pass 1's
+ *    records for every pixel, flagged or not: the G-buffer of an rm_dispatch with
+ *    AA off, bit for bit.  The refinement writes colour only.  This differs from
+ *    an rm_dispatch with AA on, whose G-buffer holds the first sample's ray: a
+ *    refined pixel's colour is the four samples' mean, its record the centre ray's.
+ *  - Fields whose bit is clear are not read and not checked.
+ *  - The environment variable RM_AA_EDGES_NAIVE (set to anything but "0"; read
+ *    by every call) selects the classifier's plain form, which tests all four
+ *    neighbours in every lane: the same mask, kept for measurement. */
+#define RM_HAS_ADAPTIVE_EDGES 1
+#define RM_AA_EDGE_COLOR   1u  /* rm_dispatch_adaptive's rule at color_threshold */
+#define RM_AA_EDGE_ID      2u  /* p.id != q.id (a miss has id -1) */
+#define RM_AA_EDGE_DEPTH   4u  /* both hit and fabsf(p.t - q.t) > depth_rel * fminf(p.t, q.t) */
+#define RM_AA_EDGE_NORMAL  8u  /* both hit and dot(p.normal, q.normal) < normal_cos */
+#define RM_AA_EDGE_ALBEDO 16u  /* some albedo component has p.albedo[c] != q.albedo[c] (checker edges) */
+
+typedef struct rm_aa_criteria {   /* 20 bytes */
+  uint32_t struct_size;           /* sizeof(rm_aa_criteria); anything else: RM_ERR_INVALID */
+  uint32_t edges;                 /* RM_AA_EDGE_* mask, non-zero, no unknown bit */
+  int32_t  color_threshold;       /* 0..255, read only under COLOR */
+  float    depth_rel;             /* >= 0, +inf allowed, not NaN; read only under DEPTH */
+  float    normal_cos;            /* in [-1, 1], not NaN; read only under NORMAL */
+} rm_aa_criteria;
+
+/* struct_size, and ID | DEPTH | NORMAL at color_threshold 8, depth_rel 0.05f,
+ * normal_cos 0.9f.  RM_ERR_INVALID for NULL. */
+int rm_aa_criteria_init(rm_aa_criteria *c);
+/* RM_ERR_INVALID for a null context (nothing written), null criteria, or a
+ * field outside the ranges above.  Asynchronous. */
+int rm_dispatch_adaptive_edges(rm_ctx *ctx, const rm_aa_criteria *criteria);
 
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process

@@ -22,58 +22,17 @@
 //                      render<>, the three-shuffle sum and store_pixel of k_sample's
 //                      sample_body, the same instantiations in the same order, so a
 //                      refined pixel is the AA-on frame's bit for bit.
+// The tile bookkeeping is rm_adaptive_tile.hpp's, shared with the geometry-edge
+// classifier (rm_adaptive_edges.hip), whose flags take the same scan, scatter and
+// refinement (launch_adapt_list below).
 // This version: whole-frame, one-device contexts; no counting build.
 #define RM_KERNELS_PIXEL_ONLY
 #define RM_KERNELS_AA_ONLY
 #include "rm_kernels.hip"
 
-#include "rm_adaptive_args.hpp"
+#include "rm_adaptive_tile.hpp"
 
 namespace rmd {
-
-// One wave per 8x8 tile, four tiles of a tile row per workgroup: a grid of 4K's
-// 130 k one-wave workgroups costs such short kernels more to launch than to run.
-constexpr int kAdaptWaves = 4;
-
-// The wave's tile column (the tile row is blockIdx.y); the last workgroup of a row
-// may hold waves past tiles_x, whose lanes are all outside the frame.
-__device__ __forceinline__ int adapt_tx() { return blockIdx.x * kAdaptWaves + (int)(threadIdx.x >> 6); }
-
-// The lane's pixel of its wave's tile; false outside the frame.
-__device__ __forceinline__ bool adapt_pixel(const AdaptArgs& A, int& px, int& py) {
-  const int lane = threadIdx.x & 63;
-  px = adapt_tx() * kAdaptTile + (lane & 7);
-  py = blockIdx.y * kAdaptTile + (lane >> 3);
-  return px < A.width && py < A.height;
-}
-
-// The flag into the context's mask, the tile's count into counts (every lane of
-// the wave calls it: the ballot is over the whole tile).
-__device__ __forceinline__ void adapt_flag(const AdaptArgs& A, bool in, int px, int py, bool flag) {
-  if (in) A.mask[(size_t)py * (size_t)A.width + (size_t)px] = flag ? 1 : 0;
-  const unsigned long long m = __ballot(in && flag);
-  if ((threadIdx.x & 63) == 0 && adapt_tx() < A.tiles_x)
-    A.counts[(size_t)blockIdx.y * (size_t)A.tiles_x + adapt_tx()] = (uint8_t)__popcll(m);
-}
-
-// max over R, G, B of |p_c - q_c| > thr on RGBA8 words (alpha takes no part)
-__device__ __forceinline__ bool adapt_differs(uint32_t p, uint32_t q, int thr) {
-  bool f = false;
-#pragma unroll
-  for (int sh = 0; sh < 24; sh += 8) {
-    const int d = (int)((p >> sh) & 255u) - (int)((q >> sh) & 255u);
-    f = f | ((d < 0 ? -d : d) > thr);
-  }
-  return f;
-}
-
-// Pass 1's pixel as its RGBA8 word: the RGBA8 image's, or the RGBA32F image's
-// floats quantised as store_pixel quantises them.
-__device__ __forceinline__ uint32_t adapt_word(const uint32_t* rgba8, const float4* rgba32f, size_t i) {
-  if (rgba8) return rgba8[i];
-  const float4 v = rgba32f[i];
-  return quantize(v.x) | (quantize(v.y) << 8) | (quantize(v.z) << 16);
-}
 
 __global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_classify(AdaptArgs A, const uint32_t* __restrict__ rgba8,
                                                        const float4* __restrict__ rgba32f, int thr) {
@@ -231,10 +190,24 @@ __global__ __launch_bounds__(64, 8) void k_adapt_refine(AdaptFrame B, AdaptArgs 
 
 namespace rm {
 
+// The scan of the tile counts a flagging kernel has written, and the scatter of the
+// flagged pixels into the list.  A's counts and offsets hold whole scan chunks
+// (rm_adaptive_args.hpp).
+hipError_t launch_adapt_list(const rmd::AdaptArgs& A, hipStream_t s) {
+  const unsigned tiles_y = (unsigned)((A.height + rmd::kAdaptTile - 1) / rmd::kAdaptTile);
+  const dim3 tiles((unsigned)((A.tiles_x + rmd::kAdaptWaves - 1) / rmd::kAdaptWaves), tiles_y), wg(64 * rmd::kAdaptWaves);
+  const size_t ntiles = (size_t)A.tiles_x * tiles_y;
+  const uint32_t nchunks = (uint32_t)((ntiles + rmd::kAdaptScanChunk - 1) / rmd::kAdaptScanChunk);
+  hipLaunchKernelGGL(rmd::k_adapt_scan, dim3(1), dim3(rmd::kAdaptScanLanes), 0, s, A.counts, A.offsets, A.total, nchunks);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rmd::k_adapt_scatter, tiles, wg, 0, s, A);
+  return hipGetLastError();
+}
+
 // mask_src: the caller's device mask at mask_pitch (k_adapt_mask), or null: colour
 // contrast above `threshold` on pass 1's image, F.rgba8 or else F.rgba32f
-// (k_adapt_classify).  Then the scan and the scatter.  A's counts and offsets hold
-// whole scan chunks (rm_adaptive_args.hpp).
+// (k_adapt_classify).  Then the scan and the scatter.
 hipError_t launch_adapt_flags(const rmd::Frame& F, const rmd::AdaptArgs& A, const void* mask_src, size_t mask_pitch,
                               int threshold, hipStream_t s) {
   const unsigned tiles_y = (unsigned)((A.height + rmd::kAdaptTile - 1) / rmd::kAdaptTile);
@@ -244,14 +217,9 @@ hipError_t launch_adapt_flags(const rmd::Frame& F, const rmd::AdaptArgs& A, cons
   else
     hipLaunchKernelGGL(rmd::k_adapt_classify, tiles, wg, 0, s, A, reinterpret_cast<const uint32_t*>(F.rgba8),
                        reinterpret_cast<const float4*>(F.rgba32f), threshold);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const size_t ntiles = (size_t)A.tiles_x * tiles_y;
-  const uint32_t nchunks = (uint32_t)((ntiles + rmd::kAdaptScanChunk - 1) / rmd::kAdaptScanChunk);
-  hipLaunchKernelGGL(rmd::k_adapt_scan, dim3(1), dim3(rmd::kAdaptScanLanes), 0, s, A.counts, A.offsets, A.total, nchunks);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(rmd::k_adapt_scatter, tiles, wg, 0, s, A);
-  return hipGetLastError();
+  return launch_adapt_list(A, s);
 }
 
 // The listed pixels of frame F of the built-in scene, on `waves` one-wave workgroups.

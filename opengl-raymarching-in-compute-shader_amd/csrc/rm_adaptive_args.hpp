@@ -1,6 +1,7 @@
 // rm_adaptive_args.hpp — the kernel arguments of adaptive supersampling
-// (rm_dispatch_adaptive / rm_dispatch_refine), shared by the
-// kernels (rm_adaptive.hip, rm_table_adaptive.hip) and the host (rm_api_adaptive.hip).
+// (rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine, DESIGN.md
+// §4.12), shared by the kernels (rm_adaptive.hip, rm_adaptive_edges.hip,
+// rm_table_adaptive.hip) and the host (rm_api_adaptive.hip).
 #pragma once
 
 #include <cstddef>
@@ -23,6 +24,17 @@ struct AdaptArgs {
   unsigned long long* total;  // [1] all flagged pixels (up to 2^32: one more than a word holds)
   uint32_t* list;             // [total] px | py << 16, tile by tile, a tile's in lane order
   int32_t width, height, tiles_x;
+};
+
+// What k_adapt_classify_edges classifies (rm_dispatch_adaptive_edges): pass 1's
+// images and the caller's criteria, checked by the host.
+struct EdgeArgs {
+  const void* gbuf;      // [height][width] rm_gbuffer_px, 16-byte aligned; read under a geometry bit
+  const void* rgba8;     // pass 1's RGBA8 image, or null: rgba32f, quantised; read under COLOR
+  const void* rgba32f;
+  uint32_t edges;        // RM_AA_EDGE_* mask
+  int32_t color_threshold;
+  float depth_rel, normal_cos;
 };
 
 }  // namespace rmd

@@ -1,22 +1,30 @@
 // rm_api_adaptive.hip — librm's C-ABI for adaptive supersampling (include/rm_api.h
-// RM_HAS_ADAPTIVE_AA): rm_dispatch_adaptive, rm_dispatch_refine /
-// _device, and the mask and the count of the last such dispatch.
+// RM_HAS_ADAPTIVE_AA, RM_HAS_ADAPTIVE_EDGES): rm_dispatch_adaptive,
+// rm_dispatch_adaptive_edges, rm_dispatch_refine / _device, and the mask and the
+// count of the last such dispatch.
 //
 // One such dispatch is, on the context's stream: pass 1 (the kernel rm_dispatch
-// would launch for the frame with AA off), the flags (rm_adaptive.hip: colour
-// contrast on pass 1's image, or the caller's mask), their scan and list, and the
-// refinement of the listed pixels (rm_adaptive.hip for the built-in scene,
-// rm_table_adaptive.hip for a table).  The host never learns the count.
+// would launch for the frame with AA off; on a G-buffer context the G-buffer
+// kernel, which writes the records too), the flags (rm_adaptive.hip: colour
+// contrast on pass 1's image, or the caller's mask; rm_adaptive_edges.hip: the
+// caller's edge criteria on pass 1's G-buffer and / or image), their scan and
+// list, and the refinement of the listed pixels (rm_adaptive.hip for the built-in
+// scene, rm_table_adaptive.hip for a table), which writes colour only.  The host
+// never learns the count.
 //
 // This version: one-device, whole-frame contexts.  Out of scope, and refused:
 // sharded, communicator and multi-device contexts (a pixel's neighbour may live
-// on another rank), G-buffer contexts, counting contexts, batches and graph
-// replay; hiprtc-specialised refine kernels (the generic table code refines);
-// any built-in criterion other than colour contrast.
+// on another rank), counting contexts, batches and graph replay; G-buffer
+// contexts for every call but rm_dispatch_adaptive_edges and the mask's and the
+// count's readers; hiprtc-specialised refine kernels (the generic table code
+// refines).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 
 #include "rm_ctx.hpp"
@@ -31,7 +39,9 @@ size_t adapt_tiles(const rm_ctx* c) {
 }
 
 // RM_ERR_STATE for the contexts this version does not serve, naming the call.
-int refuse(rm_ctx* c, const char* call) {
+// gbuf_ok: the call admits a G-buffer context (rm_dispatch_adaptive_edges, and
+// the mask's pointer for it).
+int refuse(rm_ctx* c, const char* call, bool gbuf_ok = false) {
   const std::string who = std::string(call) + ": ";
   if (!c->subs.empty() || c->cfg.ngpus >= 1)
     return fail(c, RM_ERR_STATE, who + "not available on a multi-GPU context (rm_config.ngpus)");
@@ -39,7 +49,7 @@ int refuse(rm_ctx* c, const char* call) {
     return fail(c, RM_ERR_STATE, who + "not available on a communicator context (rm_comm_init)");
   if (c->cfg.nshards > 1) return fail(c, RM_ERR_STATE, who + "not available on a sharded context (nshards > 1)");
   if (c->cfg.counters) return fail(c, RM_ERR_STATE, who + "not available with counters");
-  if (has_gbuf(c)) return fail(c, RM_ERR_STATE, who + "not available on a G-buffer context (RM_OUT_GBUFFER)");
+  if (has_gbuf(c) && !gbuf_ok) return fail(c, RM_ERR_STATE, who + "not available on a G-buffer context (RM_OUT_GBUFFER)");
   if (c->graph_on) return fail(c, RM_ERR_STATE, who + "not available with rm_graph_enable on");
   return RM_OK;
 }
@@ -82,9 +92,18 @@ int refine_waves(const rm_ctx* c) {
   return (int)std::min(groups, (size_t)c->aa_cus * kRefineWavesPerCU);
 }
 
-// One adaptive frame.  mask_src: a device mask at mask_pitch, or null for the
-// colour-contrast flags at `threshold`.
-int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int threshold) {
+// The classifier's plain form instead of its two-pair form (rm_adaptive_edges.hip):
+// RM_AA_EDGES_NAIVE set to anything but "0".  Read by every call: a measurement
+// switches it between two frames of one context.
+bool edges_naive() {
+  const char* v = std::getenv("RM_AA_EDGES_NAIVE");
+  return v && *v && std::strcmp(v, "0") != 0;
+}
+
+// One adaptive frame.  The flags: the caller's edge criteria `cr`; else a device
+// mask mask_src at mask_pitch; else (both null) colour contrast at `threshold`.
+int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int threshold,
+                   const rm_aa_criteria* cr = nullptr) {
   int rc;
   if ((rc = order_after_batch(c)) != RM_OK) return rc;
   rmd::Frame F = make_frame(c);
@@ -103,10 +122,18 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
   if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
   if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
   if ((rc = phase(c, 0)) != RM_OK) return rc;
-  hipError_t e = launch(pick_kernel(c, F), F, false, c->stream);
+  // (image_gbuf: null without RM_OUT_GBUFFER; with it pass 1 writes the records the criteria read)
+  hipError_t e = launch(pick_kernel(c, F), F, false, c->stream, image_gbuf(c));
   if (e != hipSuccess) return hip_fail(c, e, "adaptive pass 1 launch");
-  if ((e = launch_adapt_flags(F, A, mask_src, mask_pitch, threshold, c->stream)) != hipSuccess)
-    return hip_fail(c, e, "adaptive flag launch");
+  if (cr) {
+    const rmd::EdgeArgs E{image_gbuf(c), F.rgba8, F.rgba32f, cr->edges, cr->color_threshold, cr->depth_rel,
+                          cr->normal_cos};
+    e = launch_adapt_edges(A, E, !edges_naive(), c->stream);
+    if (e == hipSuccess) e = launch_adapt_list(A, c->stream);
+  } else {
+    e = launch_adapt_flags(F, A, mask_src, mask_pitch, threshold, c->stream);
+  }
+  if (e != hipSuccess) return hip_fail(c, e, "adaptive flag launch");
   e = c->nprims ? launch_table_adapt_refine(F, A, refine_waves(c), c->stream)
                 : launch_adapt_refine(F, A, refine_waves(c), c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "adaptive refine launch");
@@ -122,8 +149,8 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
 }
 
 // What every such dispatch checks and prepares before its frame.
-int begin(rm_ctx* c, const char* call) {
-  int rc = refuse(c, call);
+int begin(rm_ctx* c, const char* call, bool gbuf_ok = false) {
+  int rc = refuse(c, call, gbuf_ok);
   if (rc != RM_OK) return rc;
   if ((rc = check_uniforms(c, c->u)) != RM_OK) return rc;
   if ((rc = set_device(c)) != RM_OK) return rc;
@@ -151,6 +178,41 @@ int rm_dispatch_adaptive(rm_ctx* c, int32_t threshold) {
   return adaptive_frame(c, nullptr, 0, threshold);
 }
 
+int rm_aa_criteria_init(rm_aa_criteria* cr) {
+  if (!cr) return RM_ERR_INVALID;
+  cr->struct_size = (uint32_t)sizeof(rm_aa_criteria);
+  cr->edges = RM_AA_EDGE_ID | RM_AA_EDGE_DEPTH | RM_AA_EDGE_NORMAL;
+  cr->color_threshold = 8;
+  cr->depth_rel = 0.05f;
+  cr->normal_cos = 0.9f;
+  return RM_OK;
+}
+
+int rm_dispatch_adaptive_edges(rm_ctx* c, const rm_aa_criteria* cr) {
+  if (!c) return RM_ERR_INVALID;
+  const std::string who = "rm_dispatch_adaptive_edges: ";
+  if (!cr) return fail(c, RM_ERR_INVALID, who + "null criteria");
+  if (cr->struct_size != sizeof(rm_aa_criteria))
+    return fail(c, RM_ERR_INVALID, who + "rm_aa_criteria.struct_size is not sizeof(rm_aa_criteria)");
+  constexpr uint32_t kGeometry = RM_AA_EDGE_ID | RM_AA_EDGE_DEPTH | RM_AA_EDGE_NORMAL | RM_AA_EDGE_ALBEDO;
+  if (cr->edges == 0 || (cr->edges & ~(kGeometry | RM_AA_EDGE_COLOR)))
+    return fail(c, RM_ERR_INVALID, who + "edges must be a non-empty mask of RM_AA_EDGE_* bits");
+  if ((cr->edges & RM_AA_EDGE_COLOR) && (cr->color_threshold < 0 || cr->color_threshold > 255))
+    return fail(c, RM_ERR_INVALID, who + "color_threshold must be in 0..255");
+  // (written so that a NaN fails)
+  if ((cr->edges & RM_AA_EDGE_DEPTH) && !(cr->depth_rel >= 0.0f))
+    return fail(c, RM_ERR_INVALID, who + "depth_rel must be >= 0 (+inf allowed)");
+  if ((cr->edges & RM_AA_EDGE_NORMAL) && !(cr->normal_cos >= -1.0f && cr->normal_cos <= 1.0f))
+    return fail(c, RM_ERR_INVALID, who + "normal_cos must be in [-1, 1]");
+  if ((cr->edges & kGeometry) && !has_gbuf(c))
+    return fail(c, RM_ERR_STATE, who + "the ID, DEPTH, NORMAL and ALBEDO criteria need RM_OUT_GBUFFER in rm_config.outputs");
+  if (!(c->cfg.outputs & (RM_OUT_RGBA8 | RM_OUT_RGBA32F)))
+    return fail(c, RM_ERR_STATE, who + "the context has no colour output to refine");
+  const int rc = begin(c, "rm_dispatch_adaptive_edges", true);
+  if (rc != RM_OK) return rc;
+  return adaptive_frame(c, nullptr, 0, 0, cr);
+}
+
 int rm_dispatch_refine(rm_ctx* c, const uint8_t* mask, size_t row_pitch) {
   if (!c) return RM_ERR_INVALID;
   int rc = check_mask(c, "rm_dispatch_refine", mask, &row_pitch);
@@ -176,13 +238,13 @@ int rm_dispatch_refine_device(rm_ctx* c, const void* mask_dev, size_t row_pitch)
 int rm_read_aa_mask(rm_ctx* c, uint8_t* dst, size_t row_pitch, int flip_y) {
   if (!c) return RM_ERR_INVALID;
   if (!c->aa_dispatched)
-    return fail(c, RM_ERR_STATE, "rm_read_aa_mask: no rm_dispatch_adaptive / rm_dispatch_refine yet");
+    return fail(c, RM_ERR_STATE, "rm_read_aa_mask: no rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine yet");
   return read_image(c, c->d_aa_mask, 1, dst, row_pitch, flip_y);
 }
 
 int rm_get_aa_mask(rm_ctx* c, void** device_ptr) {
   if (!c || !device_ptr) return RM_ERR_INVALID;
-  int rc = refuse(c, "rm_get_aa_mask");
+  int rc = refuse(c, "rm_get_aa_mask", true);
   if (rc != RM_OK) return rc;
   if ((rc = set_device(c)) != RM_OK) return rc;
   if ((rc = ensure_buffers(c)) != RM_OK) return rc;
@@ -193,7 +255,7 @@ int rm_get_aa_mask(rm_ctx* c, void** device_ptr) {
 int rm_aa_refined(rm_ctx* c, int64_t* pixels) {
   if (!c || !pixels) return RM_ERR_INVALID;
   if (!c->aa_dispatched)
-    return fail(c, RM_ERR_STATE, "rm_aa_refined: no rm_dispatch_adaptive / rm_dispatch_refine yet");
+    return fail(c, RM_ERR_STATE, "rm_aa_refined: no rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine yet");
   const int rc = set_device(c);
   if (rc != RM_OK) return rc;
   unsigned long long n = 0;

@@ -55,6 +55,10 @@ hipError_t launch_table_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s);
 // the listed pixels rendered as the AA-on frame's, on `waves` one-wave workgroups
 hipError_t launch_adapt_flags(const rmd::Frame& F, const rmd::AdaptArgs& A, const void* mask_src, size_t mask_pitch,
                               int threshold, hipStream_t s);
+// the flags of the caller's edge criteria on pass 1's G-buffer and / or image
+// (rm_adaptive_edges.hip; exchange: its two-pair form), then their scan and list alone
+hipError_t launch_adapt_edges(const rmd::AdaptArgs& A, const rmd::EdgeArgs& E, bool exchange, hipStream_t s);
+hipError_t launch_adapt_list(const rmd::AdaptArgs& A, hipStream_t s);
 hipError_t launch_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
 hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
 

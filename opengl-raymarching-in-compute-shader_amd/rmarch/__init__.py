@@ -42,6 +42,12 @@ RM_OUT_RGBA32F = 2
 RM_OUT_GBUFFER = 4  # every pixel's primary hit, rm_gbuffer_px (Renderer.read_gbuffer)
 RM_HAS_GBUFFER = 1
 RM_HAS_ADAPTIVE_AA = 1  # Renderer.dispatch_adaptive / dispatch_refine
+RM_HAS_ADAPTIVE_EDGES = 1  # Renderer.dispatch_adaptive_edges: rm_aa_criteria.edges
+RM_AA_EDGE_COLOR = 1    # rm_dispatch_adaptive's rule at color_threshold
+RM_AA_EDGE_ID = 2       # p.id != q.id (a miss has id -1)
+RM_AA_EDGE_DEPTH = 4    # both hit and |p.t - q.t| > depth_rel * min(p.t, q.t)
+RM_AA_EDGE_NORMAL = 8   # both hit and dot(p.normal, q.normal) < normal_cos
+RM_AA_EDGE_ALBEDO = 16  # some albedo component differs (checker edges)
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -102,6 +108,11 @@ class rm_config(C.Structure):
                 ("row_block", C.c_int32), ("shard", C.c_int32), ("nshards", C.c_int32),
                 ("rank0_rows", C.c_int32), ("shard_format", C.c_int32), ("ngpus", C.c_int32),
                 ("devices", C.POINTER(C.c_int32))]
+
+
+class rm_aa_criteria(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("edges", C.c_uint32), ("color_threshold", C.c_int32),
+                ("depth_rel", C.c_float), ("normal_cos", C.c_float)]
 
 
 class rm_camera_state(C.Structure):
@@ -300,6 +311,8 @@ _SIGS = {
     "rm_read_aa_mask": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "rm_get_aa_mask": (C.c_int, [_P, C.POINTER(_P)]),
     "rm_aa_refined": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rm_aa_criteria_init": (C.c_int, [C.POINTER(rm_aa_criteria)]),
+    "rm_dispatch_adaptive_edges": (C.c_int, [_P, C.POINTER(rm_aa_criteria)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -614,6 +627,20 @@ class Renderer:
         if u is not None:
             self.set_uniforms(u)
         _check(lib().rm_dispatch_adaptive(self._h, int(threshold)), self._h)
+
+    def dispatch_adaptive_edges(self, u: Optional[rm_uniforms] = None,
+                                edges: int = RM_AA_EDGE_ID | RM_AA_EDGE_DEPTH | RM_AA_EDGE_NORMAL,
+                                color_threshold: int = 8, depth_rel: float = 0.05,
+                                normal_cos: float = 0.9) -> None:
+        """The same frame with the flags taken from pass 1's own G-buffer and / or image
+        (rm_dispatch_adaptive_edges): a pixel is flagged where it and a 4-neighbour satisfy
+        one of the RM_AA_EDGE_* criteria in `edges`.  The geometric criteria need
+        RM_OUT_GBUFFER; read_gbuffer() afterwards is the AA-off frame's.  Asynchronous."""
+        if u is not None:
+            self.set_uniforms(u)
+        cr = rm_aa_criteria(C.sizeof(rm_aa_criteria), int(edges), int(color_threshold), float(depth_rel),
+                            float(normal_cos))
+        _check(lib().rm_dispatch_adaptive_edges(self._h, C.byref(cr)), self._h)
 
     def dispatch_refine(self, mask, u: Optional[rm_uniforms] = None, row_pitch: int = 0) -> None:
         """The same with the caller's flags (rm_dispatch_refine): `mask` is a numpy
