@@ -51,9 +51,11 @@ __device__ __forceinline__ f3 opaque(f3 v) { return mk(opaque(v.x), opaque(v.y),
 // slack slope become constants and the miss exit's object bound is uniform.
 // PPROJ: primary rays take the projection bound of the miss exit too (k_pixel;
 // see miss_T).
+// clr: on a hit, the hit's clearance less its slack (rm_scene.hpp lazy_clearance);
+// 0, no claim, on a miss.
 template <bool COUNT, bool UNIT = false, bool PPROJ = false>
 __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3& col, Cnt& c,
-                       float& dlast) {
+                       float& dlast, float& clr) {
   float t = 0.0f, dl = 0.0f;
   const float tmax = reflected ? 200.0f : 400.0f;
   const int nmax = reflected ? 256 : 512;
@@ -219,10 +221,12 @@ __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3
       id = lazy_id(lc, t, dl, ro.y, rd.y);
       col = hit_color(id, q);
       dlast = dl;
+      clr = lazy_clearance(lc, t, rd.y);
       return t;
     }
     id = -1;
     col = mk(0.0f, 0.0f, 0.0f);
+    clr = 0.0f;
     return -1.0f;
   }
 #endif
@@ -276,21 +280,49 @@ __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3
     col = hit_color(id, q);
     if (COUNT && proven_miss) col = mk(__builtin_nanf(""), 0.0f, 0.0f);
     dlast = dl;
+    clr = lazy_clearance(lc, t, rd.y);
     return t;
   }
   id = -1;
   col = mk(0.0f, 0.0f, 0.0f);
+  clr = 0.0f;
   return -1.0f;
 }
 
+// callers without a march's clearance (ray queries, the RM_DBL probes)
+template <bool COUNT, bool UNIT = false, bool PPROJ = false>
+__device__ __forceinline__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3& col,
+                                       Cnt& c, float& dlast) {
+  float clr;
+  return march<COUNT, UNIT, PPROJ>(F, ro, rd, reflected, id, col, c, dlast, clr);
+}
+
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+
 // GetNormal glsl:278-288, samples with shared culling (rm_scene.hpp).  HAVE_C0:
 // the centre sample sdf(pos) is the primary march's last distance (same point).
-template <bool COUNT, bool HAVE_C0>
-__device__ f3 get_normal(const Frame& F, f3 pos, Cnt& c, float c0 = 0.0f) {
+// CLAIM: `claim` is clr > CLR_THR_N for the clearance clr of the march that ended
+// at pos (the caller's compare: render needs clr again for the shadow).  When it
+// holds for every active lane of the wave, the three probes see the plane alone
+// (rm_scene.hpp "the hit's clearance") and are the plane's values.  The
+// counting build takes the full samples always and checks the claim per lane:
+// a probe that differs poisons the normal, hence the sample's colour, with NaN.
+template <bool COUNT, bool HAVE_C0, bool CLAIM = false>
+__device__ f3 get_normal(const Frame& F, f3 pos, Cnt& c, float c0 = 0.0f, bool claim = false) {
   if (COUNT) c.normals++;
   RM_STAT(27);
   float vx, vy, vz;
+  if (CLAIM && !COUNT && __all(claim)) {
+    RM_STAT(21);
+    normal_samples_plane(pos, vx, vy, vz);
+    return normalize(subs(mk(vx, vy, vz), c0));
+  }
   normal_samples<HAVE_C0>(pos, F.blend, F.omblend, c0, vx, vy, vz);
+  if (CLAIM && COUNT && claim) {
+    float wx, wy, wz;
+    normal_samples_plane(pos, wx, wy, wz);
+    if (!(same_bits(vx, wx) && same_bits(vy, wy) && same_bits(vz, wz))) vx = __builtin_nanf("");
+  }
 #ifdef RM_DBL_NORMAL
   if (!COUNT) {
     float c0b = c0, wx, wy, wz;
@@ -302,18 +334,27 @@ __device__ f3 get_normal(const Frame& F, f3 pos, Cnt& c, float c0 = 0.0f) {
 }
 
 // softshadow glsl:201-216
-template <bool COUNT>
-__device__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c);
+template <bool COUNT, bool CLAIM>
+__device__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c, float clr, bool& bad);
 // rdl: |rd| (the light term's exact distance, shadow_exit_init)
-template <bool COUNT>
-__device__ __forceinline__ float softshadow(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c) {
+// CLAIM: ro lies within 0.02 (1 + 2^-20) of a hit whose clearance is clr, and rdl
+// is |rd| within 2^-20 (render: ro = pos + 0.02 normal).  Steps 0 and 1 take the
+// plane's value alone where the clearance proves, for every active lane, that no
+// object reaches below it at the step's point (rm_scene.hpp "the hit's
+// clearance"); the counting build evaluates the scene always, checks the claim
+// per lane and returns NaN where a value differs.  Other callers pass no claim.
+template <bool COUNT, bool CLAIM = false>
+__device__ __forceinline__ float softshadow(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c, float clr = 0.0f) {
+  bool bad = false;
 #ifdef RM_DBL_SHADOW
-  if (!COUNT) return vmin(softshadow_impl<COUNT>(F, ro, rd, rdl, c), softshadow_impl<COUNT>(F, opaque(ro), rd, rdl, c));
+  if (!COUNT) return vmin(softshadow_impl<COUNT, CLAIM>(F, ro, rd, rdl, c, clr, bad), softshadow_impl<COUNT, CLAIM>(F, opaque(ro), rd, rdl, c, clr, bad));
 #endif
-  return softshadow_impl<COUNT>(F, ro, rd, rdl, c);
+  const float res = softshadow_impl<COUNT, CLAIM>(F, ro, rd, rdl, c, clr, bad);
+  return (COUNT && bad) ? __builtin_nanf("") : res;
 }
-template <bool COUNT>
-__device__ __forceinline__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c) {
+template <bool COUNT, bool CLAIM>
+__device__ __forceinline__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, float rdl, Cnt& c, float clr,
+                                                 bool& bad) {
   float res = 1.0f, t = 0.0f;
   int dummy;
   RM_STAT(29);
@@ -323,7 +364,21 @@ __device__ __forceinline__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, f
       if (COUNT) c.shadow += 16 - i;
       return res;
     }
-    float h = scene_cull<false, true>(add(ro, muls(rd, t)), F.blend, F.omblend, dummy);
+    const f3 p = add(ro, muls(rd, t));
+    // steps 0 and 1 by the clearance (i is uniform: a scalar branch; one call
+    // site of scene_cull for all 16 steps)
+    const bool claim = CLAIM && i < 2 && clr > clr_thr_shadow(t, rdl);
+    float h;
+    if (!COUNT && CLAIM && i < 2 && __all(claim)) {
+#ifdef RM_STATS
+      if (i == 0) RM_STAT(22);
+      else RM_STAT(28);
+#endif
+      h = p.y + 5.5f;
+    } else {
+      h = scene_cull<false, true>(p, F.blend, F.omblend, dummy);
+      if (COUNT && claim && !same_bits(h, p.y + 5.5f)) bad = true;
+    }
     RM_STAT(2);
     if (COUNT) c.shadow++;
     if (h < 0.001f) return 0.05f;
@@ -398,9 +453,10 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT h
   int id;
   f3 hcol;
   float dl;
+  float clr;  // the hit's clearance (rm_scene.hpp): live up to the shadow call
   // (F.unit_rd is uniform: one march or the other for the whole wave)
-  float th = F.unit_rd ? march<COUNT, true, PPROJ>(F, ro, rd, false, id, hcol, c, dl)
-                       : march<COUNT, false, PPROJ>(F, ro, rd, false, id, hcol, c, dl);
+  float th = F.unit_rd ? march<COUNT, true, PPROJ>(F, ro, rd, false, id, hcol, c, dl, clr)
+                       : march<COUNT, false, PPROJ>(F, ro, rd, false, id, hcol, c, dl, clr);
 #ifdef RM_DBL_MARCH
   if (!COUNT) {
     int id2; f3 hc2; float dl2;
@@ -415,7 +471,7 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT h
   if (th != -1.0f) {
     RM_STAT(31);
     f3 pos = add(ro, muls(rd, th));
-    f3 normal = get_normal<COUNT, true>(F, pos, c, dl);
+    f3 normal = get_normal<COUNT, true, true>(F, pos, c, dl, clr > CLR_THR_N);
     if constexpr (wants_hit<HIT>::value) hit(th, id, normal, hcol);
     if (COUNT) c.lights++;
     float ldist;
@@ -428,7 +484,7 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT h
 #endif
     if (id == 7) {
       f3 lpos = mk(F.lpos[0], F.lpos[1], F.lpos[2]);
-      float sh = softshadow<COUNT>(F, add(pos, muls(normal, 0.02f)), sub(lpos, pos), ldist, c);
+      float sh = softshadow<COUNT, true>(F, add(pos, muls(normal, 0.02f)), sub(lpos, pos), ldist, c, clr);
       color = muls(color, sh);
       return gamma(color);
     }

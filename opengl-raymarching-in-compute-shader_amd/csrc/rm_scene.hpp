@@ -659,6 +659,85 @@ __device__ __forceinline__ int lazy_id(const LazyCull& lc, float t, float d, flo
   return d != plane ? lc.idb : 7;
 }
 
+// ---- the hit's clearance: the culling state reused after the march -------------------
+// At the hit step (t, point P = ro + rd t) every te[k] > t says primitive k is
+// strictly above the minimum there; the budget left says by how much.
+// Real numbers.  Each expiry that entered the running max came from a pair
+// (t_i <= t, gap_i = LB_k(p_i) - plane(p_i) - slack(t_i)) as
+// te_k = t_i + gap_i (1 - 2^-10) / (|rd| + rd.y), and (derivation above: k is
+// 1-Lipschitz along the ray, the plane linear)
+//   sdf_k(P) - plane(P) >= gap_i + slack(t_i) - (|rd| + rd.y)(t - t_i)
+//                       >= (|rd| + rd.y)(te_k - t) + slack(t_i).
+// Step 0's ball budget te_k = g_k (1 - 2^-10) / (2 |rd|), g_k = LB_k - d0 - slack,
+// bounds sdf_k(P) - min(P) >= 2 |rd| (te_k - t) + slack >= (|rd| + rd.y)(te_k - t)
+// + slack instead; with every te[k] > t no primitive is at or below the float
+// minimum of the hit step, which is then the float plane value (lazy_id: id 7),
+// so min(P) >= plane(P) - (float error of the step), and that error is what the
+// slack(0) kept on the right pays for (64 times over).  With temin = min_k te[k] > t, therefore, for all five primitives
+//   sdf_k(P) - plane(P) >= G = (|rd| + rd.y)(temin - t):   the hit's clearance.
+// What this takes from the culler: that each te[k] is a valid expiry at all,
+// which is what its (1 - 2^-10) factor (the roundings of the budget: v_rcp, the
+// fma that forms te) and its slack(t_i) (the float error of LB_k, of the plane
+// value and of p_i; the actual errors are ~2^-21 (|p|_1 + 64), slack is 2^-14 of
+// it) are there for.  The plane budget's bound above never spends that
+// slack(t_i), so it holds for the real sdfs at the real point P with the
+// culler's own margins intact.
+// What it adds, for a float point p' = fl(pos + offset) with |offset| <= r in
+// real numbers, pos = fl(ro + rd t) the float hit point:
+//   sdf_k(p') >= sdf_k(P) - r - e,  plane(p') <= plane(P) + r + e,
+//   e = |pos - P| + (the roundings that form p'),
+// so every float sdf_k(p') exceeds the float plane value (p'.y + 5.5) at p' when
+//   G > 2 r + S,   S >= 2 e + (float error of the six distances at p').
+// S = 2 slack(t) = 2 (s0 + s1 t) >= 2^-14 (|ro|_1 + 2 |rd| t + 64) >= 2^-14 (|pos|_1
+// + 64), the culler's form, rounded up as s0 and s1 are.  It covers an error of
+// up to 2^-14 (|pos|_1 + 64) >= 2^-8; e and the evaluation errors (a dozen
+// roundings of terms <= |p'|_1 + 64 each) sum to less than 2^-20 (|p'|_1 + 64),
+// and |p'|_1 <= |pos|_1 + 2 r, whose 2^-19 r is inside the margin of r below.
+// Then the scene value at p' is the plane's alone, p'.y + 5.5, bit for bit what
+// scene_cull / normal_samples return: their culled and their evaluated
+// primitives are all strictly above it, and a v_min with a larger value or a
+// skipped evaluation cannot change it.
+// lazy_clearance returns G - S, rounded toward "no claim": |rd| from below, out
+// of the slack's slope, which is live at the hit where |rd| itself no longer is
+// (s1 = 2^-14 rdl (1 + 2^-12)^2 within 2^-23, rdl within 1.5 ulp of |rd|, or 1
+// within 2^-20 of it for UNIT rays: 2^14 s1 (1 - 2^-11)^2 <= |rd| (1 - 2^-12), also
+// under cancellation with rd.y, as the absolute 2^-12 |rd| exceeds the sum's
+// rounding), the products by another 2^-12, and the final rounding is inside
+// S's 64-fold margin.  temin <= t gives <= 0, temin = -inf gives -inf or
+// (for |rd| + rd.y rounded to 0) NaN: every `clr > thr` compare then fails.  A
+// positive value implies a floor hit (above), so callers need not test the id.
+// Thresholds thr = 2 r (1 + 2^-10) with r rounded up by another (1 + 2^-10):
+//   * GetNormal's probes pos + 0.001 e_j:           r = 0.001   -> CLR_THR_N
+//   * softshadow step 0 at ro' = pos + 0.02 normal (|normal| <= 1 + 2^-20; a
+//     non-finite normal makes both forms the same NaN):  r = 0.02
+//   * softshadow step at t' on ro' + rd' t':        r = 0.02 + t' |rd'|
+//     (clr_thr_shadow; |rd'| = the light term's exact |light - pos|, within
+//     2^-22; t' = 0 gives step 0's).  A non-finite t' |rd'| fails the compare.
+// tests/test_clearance_bounds.py checks the geometry in float64; the counting
+// build evaluates both forms wherever a lane's own claim holds and poisons the
+// sample with NaN on any difference (rm_kernels.hip).
+constexpr float CLR_THR_N = 0.00201f;  // >= 2 * 0.001 (1 + 2^-10)^2 = 0.0020039
+__device__ __forceinline__ float clr_thr_shadow(float t, float rdl) {
+  // >= 2 (0.02 + t |rd|)(1 + 2^-10)^2: 2.0039072 -> 2.004, 0.0400781 -> 0.0401
+  return __builtin_fmaf(t * rdl, 2.004f, 0.0401f);
+}
+__device__ __forceinline__ float lazy_clearance(const LazyCull& lc, float t, float rdy) {
+  constexpr float RDL_LO = 16384.0f * ((1.0f - 0x1p-11f) * (1.0f - 0x1p-11f));
+  const float gl = __builtin_fmaxf(__builtin_fmaf(lc.s1, RDL_LO, rdy), 0.0f);  // <= |rd| + rd.y
+  const float S = 2.0f * __builtin_fmaf(lc.s1, t, lc.s0);
+  return __builtin_fmaf(gl * (lc.temin - t), CULL_REL_LO, -S);
+}
+// GetNormal's three probe values where the clearance proves them the plane's:
+// the same points and the same plane operation as normal_samples.
+__device__ __forceinline__ void normal_samples_plane(f3 pos, float& vx, float& vy, float& vz) {
+  const f3 px = add(pos, mk(0.001f, 0.0f, 0.0f));
+  const f3 py = add(pos, mk(0.0f, 0.001f, 0.0f));
+  const f3 pz = add(pos, mk(0.0f, 0.0f, 0.001f));
+  vx = px.y + 5.5f;
+  vy = py.y + 5.5f;
+  vz = pz.y + 5.5f;
+}
+
 // ---- provable early exits (softshadow, misses) ---------------------------------------
 // With C, R_ALL a sphere enclosing all five bounded primitives and
 // slack(t) = s0 + s1 t the float-error bound of the lazy culler, every float

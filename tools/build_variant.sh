@@ -22,7 +22,7 @@ pkg=opengl-raymarching-in-compute-shader_amd
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -I$src/include $*"
 b=$(mktemp -d)
 /opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/rm_api.hip" -o "$b/rm_api.o" &
-for f in rm_api_comm rm_api_graph rm_frame_math rm_api_trace rm_api_gbuffer; do  # the C-ABI's other files (absent in older revisions)
+for f in rm_api_comm rm_api_graph rm_frame_math rm_api_trace rm_api_gbuffer rm_api_sdf rm_api_adaptive; do  # the C-ABI's other files (absent in older revisions)
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
 /opt/rocm/bin/hipcc $flags -fno-slp-vectorize -c "$src/$pkg/csrc/rm_table.hip" -o "$b/rm_table.o" &
@@ -35,11 +35,12 @@ case "$*" in
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} $pslp -DRM_KERNELS_PIXEL_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" &
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
 esac
-# the ray-query and G-buffer kernels, as the Makefile builds them (absent in older revisions)
-for f in rm_trace rm_gbuffer; do
+# the ray-query, G-buffer, SDF-query and adaptive kernels, as the Makefile builds them
+# (absent in older revisions)
+for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
-for f in rm_table_trace rm_table_gbuffer; do
+for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags -fno-slp-vectorize -mllvm -amdgpu-inline-max-bb=8000 -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
 /opt/rocm/bin/hipcc $flags -x c++ -c "$src/$pkg/csrc/rm_host.cpp" -o "$b/rm_host.o" &

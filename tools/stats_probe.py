@@ -31,7 +31,9 @@ nm = {0: "cull-sdf(shadow)", 1: "lazy-retests", 2: "shadow-steps", 6: "refl-iter
       13: "eval-torus", 14: "eval-capsule", 15: "prim-iters", 16: "retest-sph0",
       17: "retest-sph1", 18: "retest-blend", 19: "retest-torus", 20: "retest-capsule",
       26: "bounce-iters", 27: "normals", 29: "shadows", 30: "render-after-march",
-      31: "primary-hit-shade"}
+      31: "primary-hit-shade",
+      # the clearance fast paths taken (rm_scene.hpp "the hit's clearance")
+      21: "clr-normal", 22: "clr-shadow-step0", 28: "clr-shadow-step1"}
 waves = (W * H * (4 if aa else 1) + 63) // 64
 print(f"cfg {cfg} frame {frame}: {waves} waves")
 print("%-20s %12s %14s %8s %8s" % ("point", "waves", "lanes", "lanes/w", "per wave"))
@@ -44,3 +46,7 @@ print("lazy block rate: waves %.3f lanes %.3f" % (h[9] / h[8], h[41] / h[40]))
 print("primary rays: %d misses, %.1f steps each; %d hits, %.1f steps each"
       % (h[3], h[4] / max(h[3], 1), h[23], h[5] / max(h[23], 1)))
 print("reflected: lane steps of misses %d, of hits %d" % (h[24], h[25]))
+print("clearance: plane-only normals %.3f of the normal waves (%.3f of their lanes); shadow step 0 %.3f, "
+      "step 1 %.3f of the shadow waves (%.3f, %.3f of their lanes)"
+      % (h[21] / max(h[27], 1), h[53] / max(h[59], 1), h[22] / max(h[29], 1), h[28] / max(h[29], 1),
+         h[54] / max(h[61], 1), h[60] / max(h[61], 1)))
