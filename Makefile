@@ -29,9 +29,11 @@ RM_SRCS  := $(CSRC)/rm_api.hip $(CSRC)/rm_api_comm.hip $(CSRC)/rm_api_graph.hip 
             $(CSRC)/rm_api_gbuffer.hip $(CSRC)/rm_gbuffer.hip $(CSRC)/rm_table_gbuffer.hip \
             $(CSRC)/rm_api_sdf.hip $(CSRC)/rm_sdf.hip $(CSRC)/rm_table_sdf.hip \
             $(CSRC)/rm_api_adaptive.hip $(CSRC)/rm_adaptive.hip $(CSRC)/rm_table_adaptive.hip \
-            $(CSRC)/rm_adaptive_edges.hip
+            $(CSRC)/rm_adaptive_edges.hip \
+            $(CSRC)/rm_api_mesh.hip $(CSRC)/rm_mesh.hip
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
             $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
+            $(CSRC)/rm_mesh_args.hpp \
             include/rm_api.h Makefile
 # The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
 # the names they #include each other by.
@@ -129,6 +131,13 @@ $(PKG)/build/rm_adaptive_edges.o: $(CSRC)/rm_adaptive_edges.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(KFLAGS) -c $< -o $@
 
+# The mesh-extraction kernels (rm_sdf_mesh): scene independent, in
+# an object of their own with rm_adaptive_edges.o's flags; the volume and the
+# attributes come from rm_sdf.o's / rm_table_sdf.o's kernels, unchanged.
+$(PKG)/build/rm_mesh.o: $(CSRC)/rm_mesh.hip $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(KFLAGS) -c $< -o $@
+
 $(PKG)/build/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
 	@mkdir -p $(dir $@)
 	python3 $(PKG)/tools/embed_sources.py $@ $(JIT_SRCS)
@@ -152,7 +161,8 @@ $(LIBRM): $(PKG)/build/rm_api.o $(PKG)/build/rm_api_comm.o $(PKG)/build/rm_api_g
           $(PKG)/build/rm_api_gbuffer.o $(PKG)/build/rm_gbuffer.o $(PKG)/build/rm_table_gbuffer.o \
           $(PKG)/build/rm_api_sdf.o $(PKG)/build/rm_sdf.o $(PKG)/build/rm_table_sdf.o \
           $(PKG)/build/rm_api_adaptive.o $(PKG)/build/rm_adaptive.o $(PKG)/build/rm_table_adaptive.o \
-          $(PKG)/build/rm_adaptive_edges.o
+          $(PKG)/build/rm_adaptive_edges.o \
+          $(PKG)/build/rm_api_mesh.o $(PKG)/build/rm_mesh.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
@@ -228,7 +238,8 @@ ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_f
                                       rm_api_gbuffer.o rm_gbuffer.o rm_table_gbuffer.o \
                                       rm_api_sdf.o rm_sdf.o rm_table_sdf.o \
                                       rm_api_adaptive.o rm_adaptive.o rm_table_adaptive.o \
-                                      rm_adaptive_edges.o)
+                                      rm_adaptive_edges.o \
+                                      rm_api_mesh.o rm_mesh.o)
 asan: $(ASANLIB) $(ASANORC)
 
 $(ASAN_DIR)/rm_trace.o: $(CSRC)/rm_kernels.hip

@@ -509,6 +509,90 @@ int rm_sdf_grid(rm_ctx *ctx, const rm_sdf_grid_desc *grid, float *dist, int32_t 
 /* Device outputs; asynchronous on the context's stream. */
 int rm_sdf_grid_device(rm_ctx *ctx, const rm_sdf_grid_desc *grid, void *dist_dev, void *ids_dev);
 
+/* ---- SDF mesh extraction: a surface-nets mesh of the scene from a grid -----------
+ * rm_sdf_grid gives the distance volume; these calls give the surface in it, on
+ * the device: one vertex per sign-changing cell, one quad per sign-changing grid
+ * edge, with an id, a colour and a GetNormal per vertex.  For collision meshes,
+ * export to a rasteriser or a printer, a wireframe or proxy view.  The rule below
+ * is a sequence of single IEEE operations in a fixed order and the output order
+ * follows from the grid order alone, so the mesh is reproducible bit for bit.
+ *
+ * Grid: rm_sdf_grid's.  Point (i, j, k) has the coordinate origin[a] +
+ *    (float)idx * step[a] per axis, d(i, j, k) is exactly the float rm_sdf_grid
+ *    returns for it, and the limits are the same: every dim in 0..2^24, their
+ *    product at most 2^31 - 1.
+ * Inside: a point is inside iff d < 0.0f.  NaN, +0 and -0 are outside.
+ * Cells and vertices: cell (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is
+ *    active iff its 8 corners are neither all inside nor all outside.  Active
+ *    cells are numbered in cell order, x fastest, then y, then z: that number is
+ *    the cell's vertex index.  A grid with a dim below 2 has no cell: counts
+ *    0 / 0, RM_OK, nothing written but *counts.
+ * Vertex position: the mean of the crossings on the cell's 12 edges.
+ *  - Edge order: axis a = x, y, z; with u = (a + 1) % 3 and v = (a + 2) % 3 the
+ *    edge starts at the corner offsets (du, dv) = (0,0), (1,0), (0,1), (1,1) and
+ *    runs from A to B = A + e_a.
+ *  - An edge whose ends differ in "inside" contributes a point p:
+ *    t = dA / (dA - dB); p[a] = cA + t * (cB - cA), cA and cB the two grid
+ *    coordinates on axis a; p[u] and p[v] are A's grid coordinates.
+ *  - Per component: acc = 0.0f; acc = acc + p in edge order; pos = acc /
+ *    (float)count.  Each of these is one IEEE single-precision operation in the
+ *    order written, no FMA.
+ * Quads: for every grid point A = (i, j, k) in point order (x fastest) and for
+ *    a = x, y, z in that order, the edge A -> A + e_a emits a quad iff it exists,
+ *    its ends differ in "inside", and it is interior: 1 <= A[u] <= n[u] - 2 and
+ *    1 <= A[v] <= n[v] - 2.
+ *  - The quad joins the vertices of the four cells around the edge, at the cell
+ *    offsets (du, dv) = (-1,-1), (0,-1), (0,0), (-1,0) from A; all four are
+ *    active by construction.  If A is inside the corners come in that order:
+ *    counter-clockwise seen from +a, outward normal +a.  If B is inside the
+ *    order is 0, 3, 2, 1.  Quads are numbered in emission order.
+ *  - Boundary edges emit nothing: a surface that leaves the grid ends in an open
+ *    border one cell inside it.
+ * Attributes: attr[v] is the record rm_sdf_points gives for pos[v], bit for bit:
+ *    t the residual distance, id / material / albedo the opU winner's, normal
+ *    under RM_MESH_NORMAL else 0, color 0.
+ * Capacities, as snprintf: *counts always holds the whole mesh; vertices
+ *    v < vcap and quads q < qcap are written, whole records only, and nothing
+ *    past them is touched; RM_OK either way.  A written quad may name a vertex
+ *    >= vcap.  vcap == 0 and qcap == 0 with null outputs is the count-only
+ *    query; attr == NULL skips the attributes.
+ *  - Every input gives this rule's result: any origin or step (zero, negative,
+ *    infinite or NaN; a NaN volume is all outside and gives an empty mesh) and
+ *    any iTime.
+ *
+ *  - The call uses the context's current uniforms (only iTime is read) and scene
+ *    (built-in or rm_set_scene table; generic table code under
+ *    rm_scene_specialize).  The distance volume and the per-wave bookkeeping
+ *    live in buffers the context owns, grown on demand, freed by rm_destroy.
+ *  - It is ordered on the context's stream.  It touches neither the context's
+ *    images nor its G-buffer nor its counters nor its batch ring nor its AA
+ *    mask, and is not part of graph replay.  With rm_enable_timing on, one event
+ *    pair brackets the whole sequence and it counts as one launch.
+ *  - It runs locally on sharded and communicator contexts; G-buffer and
+ *    counters contexts are allowed.  cfg.ngpus >= 1: RM_ERR_STATE.
+ *
+ * Returns RM_ERR_INVALID, nothing written, for: a null context, grid or counts;
+ * unknown flag bits; negative capacities; a null pos / indices with a capacity
+ * > 0; a pos_dev / indices_dev / attr_dev that is not 16-byte aligned; a
+ * counts_dev that is not 8-byte aligned; the grid errors of rm_sdf_grid. */
+#define RM_HAS_SDF_MESH 1
+#define RM_MESH_QUADS     0u  /* indices: [quads][4] uint32, one 16-byte record per quad */
+#define RM_MESH_TRIANGLES 1u  /* indices: [quads][6] uint32: (q0,q1,q2),(q0,q2,q3) of the same quad */
+#define RM_MESH_NORMAL    2u  /* attr[v].normal = GetNormal(pos[v]) (the bit of RM_SDF_NORMAL) */
+
+typedef struct rm_sdf_mesh_counts { uint64_t vertices, quads; } rm_sdf_mesh_counts; /* 16 bytes */
+
+/* Host outputs; synchronous.  pos: [vcap][3] float; attr: [vcap] rm_ray_hit or NULL;
+ * indices: [qcap][4 or 6] uint32.  *counts is always the whole mesh's. */
+int rm_sdf_mesh(rm_ctx *ctx, const rm_sdf_grid_desc *grid, uint32_t flags,
+                float *pos, rm_ray_hit *attr, int64_t vcap,
+                uint32_t *indices, int64_t qcap, rm_sdf_mesh_counts *counts);
+/* Device outputs; asynchronous on the context's stream; counts_dev: 8-byte aligned device
+ * memory of one rm_sdf_mesh_counts.  The host never learns the counts. */
+int rm_sdf_mesh_device(rm_ctx *ctx, const rm_sdf_grid_desc *grid, uint32_t flags,
+                       void *pos_dev, void *attr_dev, int64_t vcap,
+                       void *indices_dev, int64_t qcap, void *counts_dev);
+
 /* ---- G-buffer: every pixel's primary hit, from the frame kernels themselves ----
  * The reference's author wanted a normal and a depth view of the frame (both
  * commented out in render(), glsl:229, 248-249).  With RM_OUT_GBUFFER in

@@ -188,12 +188,14 @@ void free_all(rm_ctx* c) {
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
                    (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits,
                    &c->d_sdf_in, &c->d_sdf_out, (void**)&c->d_aa_mask, (void**)&c->d_aa_list, (void**)&c->d_aa_counts,
-                   (void**)&c->d_aa_offsets, (void**)&c->d_aa_total}) {
+                   (void**)&c->d_aa_offsets, (void**)&c->d_aa_total, &c->d_mesh_vol, &c->d_mesh_waves, &c->d_mesh_idx,
+                   &c->d_mesh_attr}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
   c->trace_cap = 0;
   c->sdf_in_cap = c->sdf_out_cap = 0;
+  c->mesh_vol_cap = c->mesh_waves_cap = c->mesh_idx_cap = c->mesh_attr_cap = 0;
   c->aa_dispatched = false;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);

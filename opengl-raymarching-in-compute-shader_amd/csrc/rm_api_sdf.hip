@@ -54,16 +54,6 @@ int check_grid(rm_ctx* c, const rm_sdf_grid_desc* g, const void* dist, const voi
   return check_uniforms(c, c->u);
 }
 
-// The query's frame constants, built as trace_launch (rm_api_trace.hip) builds
-// them: a dispatch's, without the two facts about a frame's primary rays.  The
-// sdf kernels read blend / omblend and the scene table only.
-rmd::Frame query_frame(const rm_ctx* c) {
-  rmd::Frame F = make_frame(c);
-  std::memset(F.prepv, 0, sizeof F.prepv);
-  F.unit_rd = 0;
-  return F;
-}
-
 // One kernel on the context's stream, after whatever is queued there, bracketed
 // by the timing events like a trace launch.
 template <class Launch>
@@ -90,6 +80,27 @@ int points_launch(rm_ctx* c, const void* points, int64_t n, uint32_t flags, void
 
 // Every dim >= 1; device pointers, 4-byte aligned, one of them possibly null.
 int grid_launch(rm_ctx* c, const rm_sdf_grid_desc* g, void* dist, void* ids) {
+  const rmd::SdfGridArgs G = sdf_grid_args(g, dist, ids);
+  return sdf_launch(c, [&](const rmd::Frame& F) {
+    return c->nprims ? launch_table_sdf_grid(F, G, c->stream) : launch_sdf_grid(F, G, c->stream);
+  });
+}
+
+constexpr const char* kStaging = "sdf queries: a staging buffer";
+
+}  // namespace
+
+// The query's frame constants, built as trace_launch (rm_api_trace.hip) builds
+// them: a dispatch's, without the two facts about a frame's primary rays.  The
+// sdf kernels read blend / omblend and the scene table only.
+rmd::Frame rm::query_frame(const rm_ctx* c) {
+  rmd::Frame F = make_frame(c);
+  std::memset(F.prepv, 0, sizeof F.prepv);
+  F.unit_rd = 0;
+  return F;
+}
+
+rmd::SdfGridArgs rm::sdf_grid_args(const rm_sdf_grid_desc* g, void* dist, void* ids) {
   rmd::SdfGridArgs G;
   for (int a = 0; a < 3; ++a) {
     G.origin[a] = g->origin[a];
@@ -106,14 +117,12 @@ int grid_launch(rm_ctx* c, const rm_sdf_grid_desc* g, void* dist, void* ids) {
   G.nwg = G.bpr * (uint32_t)G.ny * (uint32_t)G.nz;  // <= nx ny nz <= 2^31 - 1
   G.dist = static_cast<float*>(dist);
   G.ids = static_cast<int32_t*>(ids);
-  return sdf_launch(c, [&](const rmd::Frame& F) {
-    return c->nprims ? launch_table_sdf_grid(F, G, c->stream) : launch_sdf_grid(F, G, c->stream);
-  });
+  return G;
 }
 
-// A staging buffer of at least `need` bytes.  The host paths are synchronous, so
-// nothing of an earlier query is pending on a buffer that is replaced.
-int ensure_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need) {
+// The field queries' host paths are synchronous, and hipFree waits for the device:
+// nothing of an earlier call is pending on a buffer that is replaced.
+int rm::ensure_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need, const char* what) {
   if (need <= *cap) return RM_OK;
   if (*buf) (void)hipFree(*buf);
   *buf = nullptr;
@@ -123,13 +132,11 @@ int ensure_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need) {
   if (hipMalloc(buf, n) != hipSuccess) {
     *buf = nullptr;
     (void)hipGetLastError();
-    return fail(c, RM_ERR_NOMEM, "sdf queries: a staging buffer of " + std::to_string(need) + " bytes");
+    return fail(c, RM_ERR_NOMEM, std::string(what) + " of " + std::to_string(need) + " bytes");
   }
   *cap = n;
   return RM_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -151,8 +158,8 @@ int rm_sdf_points(rm_ctx* c, const float* points, int64_t n, uint32_t flags, rm_
   if (n == 0) return RM_OK;
   if ((rc = set_device(c)) != RM_OK) return rc;
   const size_t pb = (size_t)n * 3 * sizeof(float), ob = (size_t)n * sizeof(rm_ray_hit);
-  if ((rc = ensure_bytes(c, &c->d_sdf_in, &c->sdf_in_cap, pb)) != RM_OK) return rc;
-  if ((rc = ensure_bytes(c, &c->d_sdf_out, &c->sdf_out_cap, ob)) != RM_OK) return rc;
+  if ((rc = ensure_bytes(c, &c->d_sdf_in, &c->sdf_in_cap, pb, kStaging)) != RM_OK) return rc;
+  if ((rc = ensure_bytes(c, &c->d_sdf_out, &c->sdf_out_cap, ob, kStaging)) != RM_OK) return rc;
   RM_HIP(c, hipMemcpyAsync(c->d_sdf_in, points, pb, hipMemcpyHostToDevice, c->stream));
   if ((rc = points_launch(c, c->d_sdf_in, n, flags, c->d_sdf_out)) != RM_OK) return rc;
   RM_HIP(c, hipMemcpyAsync(out, c->d_sdf_out, ob, hipMemcpyDeviceToHost, c->stream));
@@ -181,8 +188,8 @@ int rm_sdf_grid(rm_ctx* c, const rm_sdf_grid_desc* grid, float* dist, int32_t* i
   if ((rc = set_device(c)) != RM_OK) return rc;
   // the points' staging buffer holds the ids, the records' the distances
   const size_t b = (size_t)total * 4;
-  if (ids && (rc = ensure_bytes(c, &c->d_sdf_in, &c->sdf_in_cap, b)) != RM_OK) return rc;
-  if (dist && (rc = ensure_bytes(c, &c->d_sdf_out, &c->sdf_out_cap, b)) != RM_OK) return rc;
+  if (ids && (rc = ensure_bytes(c, &c->d_sdf_in, &c->sdf_in_cap, b, kStaging)) != RM_OK) return rc;
+  if (dist && (rc = ensure_bytes(c, &c->d_sdf_out, &c->sdf_out_cap, b, kStaging)) != RM_OK) return rc;
   if ((rc = grid_launch(c, grid, dist ? c->d_sdf_out : nullptr, ids ? c->d_sdf_in : nullptr)) != RM_OK) return rc;
   if (dist) RM_HIP(c, hipMemcpyAsync(dist, c->d_sdf_out, b, hipMemcpyDeviceToHost, c->stream));
   if (ids) RM_HIP(c, hipMemcpyAsync(ids, c->d_sdf_in, b, hipMemcpyDeviceToHost, c->stream));

@@ -2,7 +2,8 @@
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
 // rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
-// rm_api_sdf.hip (SDF field queries) and rm_api_adaptive.hip (adaptive supersampling).
+// rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling) and
+// rm_api_mesh.hip (SDF mesh extraction).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -16,6 +17,7 @@
 #include "rm_comm.hpp"
 #include "rm_internal.hpp"
 #include "rm_jit.hpp"
+#include "rm_mesh_args.hpp"
 #include "rm_scene.hpp"
 #include "rm_sdf_args.hpp"
 
@@ -61,6 +63,13 @@ hipError_t launch_adapt_edges(const rmd::AdaptArgs& A, const rmd::EdgeArgs& E, b
 hipError_t launch_adapt_list(const rmd::AdaptArgs& A, hipStream_t s);
 hipError_t launch_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
 hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
+// SDF mesh extraction (rm_mesh.hip), every dim >= 2: the waves' ballots and counts of M.vol,
+// their scans and the mesh's counts; then the vertices below M.vcap and the quads below
+// M.qcap; the device call's records below min(counts[0], vcap) out of n >= 1 staged ones
+hipError_t launch_mesh_count(const rmd::MeshArgs& M, hipStream_t s);
+hipError_t launch_mesh_emit(const rmd::MeshArgs& M, hipStream_t s);
+hipError_t launch_mesh_attr_copy(const void* src, void* dst, const void* counts, int64_t vcap, int64_t n,
+                                 hipStream_t s);
 
 // Which kernel renders a frame (rm_api.hip pick_kernel): the built-in scene's, or
 // for a runtime scene table its specialised kernels (jit) or the generic table
@@ -192,6 +201,14 @@ struct rm_ctx {
   bool aa_dispatched = false;  // the mask and the total are those of a dispatch
   int aa_waves_env = 0;        // RM_AA_REFINE_WAVES at rm_create (0: unset)
   int aa_cus = 0;              // the device's compute units (first adaptive dispatch)
+  // SDF mesh extraction (rm_api_mesh.hip), grown on demand (bytes): the distance volume; the
+  // counts and the per-wave arrays (rm_mesh_args.hpp); rm_sdf_mesh's staging of the indices
+  // (its positions and records use d_sdf_in / d_sdf_out); rm_sdf_mesh_device's of the records
+  void* d_mesh_vol = nullptr;
+  void* d_mesh_waves = nullptr;
+  void* d_mesh_idx = nullptr;
+  void* d_mesh_attr = nullptr;
+  size_t mesh_vol_cap = 0, mesh_waves_cap = 0, mesh_idx_cap = 0, mesh_attr_cap = 0;
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;
@@ -296,6 +313,16 @@ int comm_gather(rm_ctx* c);
 int comm_assemble(rm_ctx* c);
 int multi_frame(rm_ctx* c, bool graph);
 int comm_batch(rm_ctx* c, const rm_uniforms* u, int n);
+
+// ---- rm_api_sdf.hip: what the field queries share with the mesh extraction (rm_api_mesh.hip) ----
+// The query's frame constants: a dispatch's, without the two facts about a frame's primary rays.
+rmd::Frame query_frame(const rm_ctx* c);
+// The grid kernels' arguments for a grid of dims >= 1 and device outputs (4-byte aligned, one
+// of them possibly null): the lane mapping is chosen from nx and the outputs' alignment.
+rmd::SdfGridArgs sdf_grid_args(const rm_sdf_grid_desc* g, void* dist, void* ids);
+// A context-owned device buffer of at least `need` bytes, replaced when too small (hipFree
+// waits for the device, so nothing pending uses the old one); `what` names it in RM_ERR_NOMEM.
+int ensure_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need, const char* what);
 
 // ---- rm_api_graph.hip: hipGraph replay -----------------------------------------------------
 void graph_release(rm_ctx* c);

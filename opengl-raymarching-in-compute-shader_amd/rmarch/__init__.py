@@ -66,6 +66,11 @@ RM_TRACE_SHADOW = 8     # alone: t = softshadow(ro, rd, k)
 RM_HAS_SDF_QUERY = 1
 RM_SDF_VALUE = 0        # sdf(p): t = the distance (negative inside), id, material, albedo
 RM_SDF_NORMAL = 2       # + GetNormal(p) (the same bit as RM_TRACE_NORMAL)
+# SDF mesh extraction (rm_sdf_mesh): flags
+RM_HAS_SDF_MESH = 1
+RM_MESH_QUADS = 0       # indices: [quads][4] uint32
+RM_MESH_TRIANGLES = 1   # indices: [quads][6] uint32: (q0, q1, q2), (q0, q2, q3) of the same quad
+RM_MESH_NORMAL = 2      # attr[v].normal = GetNormal(pos[v]) (the bit of RM_SDF_NORMAL)
 
 
 class RMError(RuntimeError):
@@ -154,6 +159,13 @@ class rm_sdf_grid_desc(C.Structure):
 
 
 assert C.sizeof(rm_sdf_grid_desc) == 36
+
+
+class rm_sdf_mesh_counts(C.Structure):
+    _fields_ = [("vertices", C.c_uint64), ("quads", C.c_uint64)]
+
+
+assert C.sizeof(rm_sdf_mesh_counts) == 16
 
 
 class rm_gbuffer_px(C.Structure):
@@ -302,6 +314,9 @@ _SIGS = {
     "rm_sdf_points_device": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P]),
     "rm_sdf_grid": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), _P, _P]),
     "rm_sdf_grid_device": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), _P, _P]),
+    "rm_sdf_mesh": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), C.c_uint32, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "rm_sdf_mesh_device": (C.c_int, [_P, C.POINTER(rm_sdf_grid_desc), C.c_uint32, _P, _P, C.c_int64, _P, C.c_int64,
+                                     _P]),
     "rm_read_gbuffer": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "rm_set_output_gbuffer": (C.c_int, [_P, _P]),
     "rm_get_output_gbuffer": (C.c_int, [_P, C.POINTER(_P)]),
@@ -824,6 +839,57 @@ class Renderer:
             _check(lib().rm_sdf_grid(self._h, C.byref(g), dist.ctypes.data,
                                      idt.ctypes.data if ids else None), self._h)
         return (dist, idt) if ids else dist
+
+    # -- SDF mesh extraction (rm_sdf_mesh)
+    def sdf_mesh(self, origin, step, dims, *, triangles: bool = False, normals: bool = False, attrs: bool = True,
+                 device: bool = False, max_vertices: Optional[int] = None, max_quads: Optional[int] = None):
+        """The surface-nets mesh of the scene on sdf_grid's grid (rm_sdf_mesh): one vertex per
+        sign-changing cell, one quad per interior sign-changing grid edge, in grid order.
+
+        Host (the default): a count-only call, then exact-size numpy arrays.  Returns
+        (pos, indices, attr): pos (V, 3) float32; indices (Q, 4) uint32, or (Q, 6) with
+        triangles=True; attr a RAY_HIT_DTYPE array of V records (rm_sdf_points' at pos, with
+        GetNormal under normals=True), or None with attrs=False.
+
+        device=True: asynchronous on the context's stream into torch tensors of the
+        capacities max_vertices / max_quads (both required); returns (pos, indices, attr,
+        counts), attr an (max_vertices, 12) float32 tensor or None, counts an int64 tensor
+        (vertices, quads) of the whole mesh.  Only the records below min(count, capacity)
+        are written (rm_sdf_mesh_device)."""
+        nx, ny, nz = (int(d) for d in dims)
+        g = rm_sdf_grid_desc((C.c_float * 3)(*[float(v) for v in origin]),
+                             (C.c_float * 3)(*[float(v) for v in step]), (C.c_int32 * 3)(nx, ny, nz))
+        flags = (RM_MESH_TRIANGLES if triangles else 0) | (RM_MESH_NORMAL if normals else 0)
+        per = 6 if triangles else 4
+        if device:
+            import torch
+            if self.device < 0:
+                raise RuntimeError("sdf_mesh: device=True needs torch loaded when the context was created")
+            if max_vertices is None or max_quads is None:
+                raise ValueError("sdf_mesh: device=True needs max_vertices and max_quads")
+            vcap, qcap = int(max_vertices), int(max_quads)
+            dev = torch.device("cuda", self.device)
+            pos = torch.empty((vcap, 3), dtype=torch.float32, device=dev)
+            idx = torch.empty((qcap, per), dtype=torch.int32, device=dev)  # (torch has no uint32 arithmetic)
+            attr = torch.empty((vcap, 12), dtype=torch.float32, device=dev) if attrs else None
+            # empty, as every output here: the library always writes the counts (zeros for a grid
+            # without a cell) on the context's stream, and a fill queued on torch's could land after it
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            _check(lib().rm_sdf_mesh_device(self._h, C.byref(g), flags, pos.data_ptr() if vcap else None,
+                                            attr.data_ptr() if attrs and vcap else None, vcap,
+                                            idx.data_ptr() if qcap else None, qcap, counts.data_ptr()), self._h)
+            return pos, idx, attr, counts
+        n = rm_sdf_mesh_counts()
+        _check(lib().rm_sdf_mesh(self._h, C.byref(g), flags, None, None, 0, None, 0, C.byref(n)), self._h)
+        nv, nq = int(n.vertices), int(n.quads)
+        pos = np.empty((nv, 3), np.float32)
+        idx = np.empty((nq, per), np.uint32)
+        attr = np.empty(nv, RAY_HIT_DTYPE) if attrs else None
+        if nv or nq:
+            _check(lib().rm_sdf_mesh(self._h, C.byref(g), flags, pos.ctypes.data if nv else None,
+                                     attr.ctypes.data if attrs and nv else None, nv,
+                                     idx.ctypes.data if nq else None, nq, C.byref(n)), self._h)
+        return pos, idx, attr
 
     # -- device interop
     def set_stream(self, stream_ptr: Optional[int]) -> None:
