@@ -30,7 +30,7 @@ RM_SRCS  := $(CSRC)/rm_api.hip $(CSRC)/rm_api_comm.hip $(CSRC)/rm_api_graph.hip 
             $(CSRC)/rm_api_sdf.hip $(CSRC)/rm_sdf.hip $(CSRC)/rm_table_sdf.hip \
             $(CSRC)/rm_api_adaptive.hip $(CSRC)/rm_adaptive.hip $(CSRC)/rm_table_adaptive.hip \
             $(CSRC)/rm_adaptive_edges.hip \
-            $(CSRC)/rm_api_mesh.hip $(CSRC)/rm_mesh.hip
+            $(CSRC)/rm_api_mesh.hip $(CSRC)/rm_mesh.hip $(CSRC)/rm_api_query.hip
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
             $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
             $(CSRC)/rm_mesh_args.hpp \
@@ -162,7 +162,7 @@ $(LIBRM): $(PKG)/build/rm_api.o $(PKG)/build/rm_api_comm.o $(PKG)/build/rm_api_g
           $(PKG)/build/rm_api_sdf.o $(PKG)/build/rm_sdf.o $(PKG)/build/rm_table_sdf.o \
           $(PKG)/build/rm_api_adaptive.o $(PKG)/build/rm_adaptive.o $(PKG)/build/rm_table_adaptive.o \
           $(PKG)/build/rm_adaptive_edges.o \
-          $(PKG)/build/rm_api_mesh.o $(PKG)/build/rm_mesh.o
+          $(PKG)/build/rm_api_mesh.o $(PKG)/build/rm_mesh.o $(PKG)/build/rm_api_query.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
@@ -239,7 +239,7 @@ ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_f
                                       rm_api_sdf.o rm_sdf.o rm_table_sdf.o \
                                       rm_api_adaptive.o rm_adaptive.o rm_table_adaptive.o \
                                       rm_adaptive_edges.o \
-                                      rm_api_mesh.o rm_mesh.o)
+                                      rm_api_mesh.o rm_mesh.o rm_api_query.o)
 asan: $(ASANLIB) $(ASANORC)
 
 $(ASAN_DIR)/rm_trace.o: $(CSRC)/rm_kernels.hip

@@ -159,6 +159,16 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
   return k;
 }
 
+// The same decision for the kernels that are not frame kernels: the built-in
+// scene's, or for a table always the generic code (its specialised kernels render
+// frames only).
+const SceneKernels& rm::scene_kernels(const rm_ctx* c) {
+  static const SceneKernels builtin{launch_trace, launch_sdf_points, launch_sdf_grid, launch_adapt_refine};
+  static const SceneKernels table{launch_table_trace, launch_table_sdf_points, launch_table_sdf_grid,
+                                  launch_table_adapt_refine};
+  return c->nprims ? table : builtin;
+}
+
 hipError_t rm::launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s, void* gbuf) {
   if (k.gbuf) {
     // (rm_create refuses counters with the bit; a missing image is an error, not a plain frame)
@@ -186,16 +196,15 @@ void free_all(rm_ctx* c) {
   c->comm = nullptr;
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
-                   (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_trace_rays, (void**)&c->d_trace_hits,
-                   &c->d_sdf_in, &c->d_sdf_out, (void**)&c->d_aa_mask, (void**)&c->d_aa_list, (void**)&c->d_aa_counts,
-                   (void**)&c->d_aa_offsets, (void**)&c->d_aa_total, &c->d_mesh_vol, &c->d_mesh_waves, &c->d_mesh_idx,
-                   &c->d_mesh_attr}) {
+                   (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_aa_mask, (void**)&c->d_aa_list,
+                   (void**)&c->d_aa_counts, (void**)&c->d_aa_offsets, (void**)&c->d_aa_total}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  c->trace_cap = 0;
-  c->sdf_in_cap = c->sdf_out_cap = 0;
-  c->mesh_vol_cap = c->mesh_waves_cap = c->mesh_idx_cap = c->mesh_attr_cap = 0;
+  for (DevBuf* b : {&c->stage_in, &c->stage_out, &c->mesh_vol, &c->mesh_waves, &c->mesh_idx, &c->mesh_attr}) {
+    if (b->p) (void)hipFree(b->p);
+    *b = DevBuf();
+  }
   c->aa_dispatched = false;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);
@@ -471,21 +480,26 @@ int rm_get_uniforms(const rm_ctx* c, rm_uniforms* u) {
 
 // ---- dispatch ---------------------------------------------------------------------
 
-// Timing events for the next launch (rm_enable_timing), or nulls.
-int rm::timing_events(rm_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
-  *e0 = *e1 = nullptr;
+// The context's next event pair (rm_ctx.hpp Timed), created on first use; the
+// pairs below ev_used are claimed and wait for rm_kernel_time_ms.
+int rm::Timed::begin(rm_ctx* c) {
   if (!c->timing) return RM_OK;
   if (c->ev_used == c->ev_pool.size()) {
     std::pair<hipEvent_t, hipEvent_t> p;
     RM_HIP(c, hipEventCreate(&p.first));
     RM_HIP(c, hipEventCreate(&p.second));
     c->ev_pool.push_back(p);
+    c->ev_frames.push_back(1);
   }
-  *e0 = c->ev_pool[c->ev_used].first;
-  *e1 = c->ev_pool[c->ev_used].second;
-  if (c->ev_frames.size() < c->ev_pool.size()) c->ev_frames.resize(c->ev_pool.size(), 1);
-  c->ev_frames[c->ev_used] = 1;
-  c->ev_used++;
+  RM_HIP(c, hipEventRecord(c->ev_pool[c->ev_used].first, c->stream));
+  on = true;
+  return RM_OK;
+}
+
+int rm::Timed::end(rm_ctx* c, int frames) {
+  if (!on) return RM_OK;
+  RM_HIP(c, hipEventRecord(c->ev_pool[c->ev_used].second, c->stream));
+  c->ev_frames[c->ev_used++] = frames;
   return RM_OK;
 }
 
@@ -510,12 +524,11 @@ int rm::render_launch(rm_ctx* c) {
     RM_HIP(c, hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), c->stream));
   }
   rmd::Frame F = make_frame(c);
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   const hipError_t e = launch(pick_kernel(c, F), F, c->cfg.counters != 0, c->stream, image_gbuf(c));
   if (e != hipSuccess) return hip_fail(c, e, "kernel launch");
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
+  if ((rc = t.end(c)) != RM_OK) return rc;
   c->dispatched = true;
   return RM_OK;
 }
@@ -597,16 +610,12 @@ static int plain_batch(rm_ctx* c, const rm_uniforms* u, int n) {
     out8[k] = dst8 ? (k < n - 1 ? c->ring8[k] : dst8) : nullptr;
     out32[k] = dst32 ? (k < n - 1 ? c->ring32[k] : dst32) : nullptr;
   }
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   if ((rc = phase(c, 0)) != RM_OK) return rc;
   if ((rc = launch_batch(c, u, n, out8, out32)) != RM_OK) return rc;
   if ((rc = phase(c, 1)) != RM_OK) return rc;
-  if (e1) {
-    RM_HIP(c, hipEventRecord(e1, c->stream));
-    c->ev_frames[c->ev_used - 1] = n;
-  }
+  if ((rc = t.end(c, n)) != RM_OK) return rc;
   if (c->timing) {
     c->ph_recorded = true;
     c->ph_comm = false;
@@ -1012,7 +1021,7 @@ int rm_kernel_time_ms(rm_ctx* c, double* total_ms, int64_t* launches, int reset)
     float ms = 0.0f;
     RM_HIP(c, hipEventElapsedTime(&ms, c->ev_pool[i].first, c->ev_pool[i].second));
     c->total_ms += ms;
-    c->launches += i < c->ev_frames.size() ? c->ev_frames[i] : 1;  // a batch counts its frames
+    c->launches += c->ev_frames[i];  // a batch counts its frames
   }
   c->ev_used = 0;
   if (total_ms) *total_ms = c->total_ms;

@@ -118,9 +118,8 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
   A.width = c->cfg.width;
   A.height = c->cfg.height;
   A.tiles_x = (c->cfg.width + rmd::kAdaptTile - 1) / rmd::kAdaptTile;
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   if ((rc = phase(c, 0)) != RM_OK) return rc;
   // (image_gbuf: null without RM_OUT_GBUFFER; with it pass 1 writes the records the criteria read)
   hipError_t e = launch(pick_kernel(c, F), F, false, c->stream, image_gbuf(c));
@@ -134,11 +133,10 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
     e = launch_adapt_flags(F, A, mask_src, mask_pitch, threshold, c->stream);
   }
   if (e != hipSuccess) return hip_fail(c, e, "adaptive flag launch");
-  e = c->nprims ? launch_table_adapt_refine(F, A, refine_waves(c), c->stream)
-                : launch_adapt_refine(F, A, refine_waves(c), c->stream);
+  e = scene_kernels(c).adapt_refine(F, A, refine_waves(c), c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "adaptive refine launch");
   if ((rc = phase(c, 1)) != RM_OK) return rc;
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
+  if ((rc = t.end(c)) != RM_OK) return rc;
   if (c->timing) {
     c->ph_recorded = true;
     c->ph_comm = false;

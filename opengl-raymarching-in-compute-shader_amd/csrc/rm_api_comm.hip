@@ -442,9 +442,8 @@ int batch_render(rm_ctx* c, const rm_uniforms* u, int n) {
   // the slot's previous batch (two batches ago) has been gathered and assembled
   if (b.pending) RM_HIP(c, hipStreamWaitEvent(c->stream, b.freed, 0));
   const size_t px = (size_t)c->rows * (size_t)c->cfg.width;
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   if ((rc = phase(c, 0)) != RM_OK) return rc;
   uint8_t* out8[RM_MAX_BATCH];
   float* out32[RM_MAX_BATCH];
@@ -454,10 +453,7 @@ int batch_render(rm_ctx* c, const rm_uniforms* u, int n) {
   }
   if ((rc = launch_batch(c, u, n, out8, out32)) != RM_OK) return rc;
   if ((rc = phase(c, 1)) != RM_OK) return rc;
-  if (e1) {
-    RM_HIP(c, hipEventRecord(e1, c->stream));
-    c->ev_frames[c->ev_used - 1] = n;
-  }
+  if ((rc = t.end(c, n)) != RM_OK) return rc;
   RM_HIP(c, hipEventRecord(b.rendered, c->stream));
   return RM_OK;
 }

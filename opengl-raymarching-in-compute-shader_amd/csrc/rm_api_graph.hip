@@ -96,11 +96,10 @@ int rm::graph_frame(rm_ctx* c) {
   kp.kernelParams = args;
   kp.extra = nullptr;
   RM_HIP(c, hipGraphExecKernelNodeSetParams(g.exec, g.render, &kp));
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   RM_HIP(c, hipGraphLaunch(g.exec, c->stream));
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
+  if ((rc = t.end(c)) != RM_OK) return rc;
   c->dispatched = true;
   return RM_OK;
 }

@@ -18,27 +18,22 @@ static_assert(RM_MESH_NORMAL == RM_SDF_NORMAL, "RM_MESH_NORMAL is the point kern
 namespace {
 
 constexpr uint32_t kAllFlags = RM_MESH_TRIANGLES | RM_MESH_NORMAL;
-constexpr int32_t kMaxDim = 1 << 24;
 
 // What both entry points refuse before any device call; the grid errors are
-// rm_sdf_grid's (rm_api_sdf.hip check_grid).  *cells: the grid's cells, 0 for a
-// grid with a dim below 2.
+// rm_sdf_grid's (grid_points).  *cells: the grid's cells, 0 for a grid with a dim
+// below 2.
 int check_mesh(rm_ctx* c, const rm_sdf_grid_desc* g, uint32_t flags, const void* pos, int64_t vcap,
                const void* indices, int64_t qcap, const void* counts, int64_t* cells) {
-  if (!c->subs.empty()) return fail(c, RM_ERR_STATE, "sdf mesh: not available on a multi-device context (cfg.ngpus)");
+  int rc = refuse_multi(c, "sdf mesh");
+  if (rc != RM_OK) return rc;
   if (!g) return fail(c, RM_ERR_INVALID, "sdf mesh: null descriptor");
   if (!counts) return fail(c, RM_ERR_INVALID, "sdf mesh: null counts");
   if (flags & ~kAllFlags) return fail(c, RM_ERR_INVALID, "sdf mesh: unknown flag bits");
   if (vcap < 0 || qcap < 0) return fail(c, RM_ERR_INVALID, "sdf mesh: negative capacity");
   if ((vcap > 0 && !pos) || (qcap > 0 && !indices))
     return fail(c, RM_ERR_INVALID, "sdf mesh: null output with a capacity above 0");
-  for (int a = 0; a < 3; ++a)
-    if (g->dims[a] < 0 || g->dims[a] > kMaxDim)
-      return fail(c, RM_ERR_INVALID, "sdf mesh: every dim must be in 0..2^24");
-  int64_t t = (int64_t)g->dims[0] * g->dims[1];  // <= 2^48
-  if (t > INT32_MAX && g->dims[2] != 0) return fail(c, RM_ERR_INVALID, "sdf mesh: more than 2^31 - 1 points");
-  t = g->dims[2] == 0 ? 0 : t * g->dims[2];      // <= 2^55
-  if (t > INT32_MAX) return fail(c, RM_ERR_INVALID, "sdf mesh: more than 2^31 - 1 points");
+  int64_t points;
+  if ((rc = grid_points(c, "sdf mesh", g, &points)) != RM_OK) return rc;
   *cells = 0;
   if (g->dims[0] >= 2 && g->dims[1] >= 2 && g->dims[2] >= 2)
     *cells = (int64_t)(g->dims[0] - 1) * (g->dims[1] - 1) * (g->dims[2] - 1);
@@ -63,11 +58,11 @@ int mesh_args(rm_ctx* c, const rm_sdf_grid_desc* g, rmd::MeshArgs* M) {
   const size_t points = (size_t)M->nx * M->ny * M->nz;
   const size_t nwp = ((size_t)M->nw + rmd::kMeshScanChunk - 1) / rmd::kMeshScanChunk * rmd::kMeshScanChunk;
   int rc;
-  if ((rc = ensure_bytes(c, &c->d_mesh_vol, &c->mesh_vol_cap, points * 4, kBuffer)) != RM_OK) return rc;
+  if ((rc = ensure(c, c->mesh_vol, points * 4, kBuffer)) != RM_OK) return rc;
   const size_t wave_bytes = 16 + nwp / rmd::kMeshScanChunk * 16 + nwp * (32 + 8 + 4 + 4 + 1 + 1);
-  if ((rc = ensure_bytes(c, &c->d_mesh_waves, &c->mesh_waves_cap, wave_bytes, kBuffer)) != RM_OK) return rc;
-  M->vol = static_cast<const float*>(c->d_mesh_vol);
-  uint8_t* p = static_cast<uint8_t*>(c->d_mesh_waves);
+  if ((rc = ensure(c, c->mesh_waves, wave_bytes, kBuffer)) != RM_OK) return rc;
+  M->vol = static_cast<const float*>(c->mesh_vol.p);
+  uint8_t* p = static_cast<uint8_t*>(c->mesh_waves.p);
   M->counts = reinterpret_cast<unsigned long long*>(p);
   p += 16;
   M->chunks = reinterpret_cast<unsigned long long*>(p);
@@ -93,17 +88,15 @@ int mesh_args(rm_ctx* c, const rm_sdf_grid_desc* g, rmd::MeshArgs* M) {
 // The volume of the scene into the context's buffer, then the ballots, the scans
 // and the counts: on the context's stream, by the field queries' grid kernel.
 int mesh_count(rm_ctx* c, const rm_sdf_grid_desc* g, const rmd::Frame& F, const rmd::MeshArgs& M) {
-  const rmd::SdfGridArgs G = sdf_grid_args(g, c->d_mesh_vol, nullptr);  // rm_sdf_grid_device's, dist only
-  hipError_t e = c->nprims ? launch_table_sdf_grid(F, G, c->stream) : launch_sdf_grid(F, G, c->stream);
+  const rmd::SdfGridArgs G = sdf_grid_args(g, c->mesh_vol.p, nullptr);  // rm_sdf_grid_device's, dist only
+  hipError_t e = scene_kernels(c).sdf_grid(F, G, c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "sdf mesh: grid kernel launch");
   if ((e = launch_mesh_count(M, c->stream)) != hipSuccess) return hip_fail(c, e, "sdf mesh: count kernel launch");
   return RM_OK;
 }
 
 int points_launch(rm_ctx* c, const rmd::Frame& F, const void* points, int64_t n, uint32_t flags, void* out) {
-  const uint32_t pf = flags & RM_MESH_NORMAL;
-  const hipError_t e = c->nprims ? launch_table_sdf_points(F, points, out, n, pf, c->stream)
-                                 : launch_sdf_points(F, points, out, n, pf, c->stream);
+  const hipError_t e = scene_kernels(c).sdf_points(F, points, out, n, flags & RM_MESH_NORMAL, c->stream);
   return e == hipSuccess ? RM_OK : hip_fail(c, e, "sdf mesh: point kernel launch");
 }
 
@@ -137,11 +130,10 @@ int rm_sdf_mesh_device(rm_ctx* c, const rm_sdf_grid_desc* grid, uint32_t flags, 
   // a staging copy, of which the records below the count go to the caller's array
   const int64_t nattr = attr_dev ? (vcap < cells ? vcap : cells) : 0;
   const size_t attr_bytes = (size_t)nattr * sizeof(rm_ray_hit);
-  if (nattr > 0 && (rc = ensure_bytes(c, &c->d_mesh_attr, &c->mesh_attr_cap, attr_bytes, kBuffer)) != RM_OK) return rc;
+  if (nattr > 0 && (rc = ensure(c, c->mesh_attr, attr_bytes, kBuffer)) != RM_OK) return rc;
   const rmd::Frame F = query_frame(c);
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   if ((rc = mesh_count(c, grid, F, M)) != RM_OK) return rc;
   RM_HIP(c, hipMemcpyAsync(counts_dev, M.counts, sizeof(rm_sdf_mesh_counts), hipMemcpyDeviceToDevice, c->stream));
   M.pos = static_cast<float*>(pos_dev);
@@ -152,12 +144,11 @@ int rm_sdf_mesh_device(rm_ctx* c, const rm_sdf_grid_desc* grid, uint32_t flags, 
   hipError_t e = launch_mesh_emit(M, c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "sdf mesh: emit kernel launch");
   if (nattr > 0) {
-    if ((rc = points_launch(c, F, pos_dev, nattr, flags, c->d_mesh_attr)) != RM_OK) return rc;
-    if ((e = launch_mesh_attr_copy(c->d_mesh_attr, attr_dev, M.counts, vcap, nattr, c->stream)) != hipSuccess)
+    if ((rc = points_launch(c, F, pos_dev, nattr, flags, c->mesh_attr.p)) != RM_OK) return rc;
+    if ((e = launch_mesh_attr_copy(c->mesh_attr.p, attr_dev, M.counts, vcap, nattr, c->stream)) != hipSuccess)
       return hip_fail(c, e, "sdf mesh: attribute copy launch");
   }
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
-  return RM_OK;
+  return t.end(c);
 }
 
 int rm_sdf_mesh(rm_ctx* c, const rm_sdf_grid_desc* grid, uint32_t flags, float* pos, rm_ray_hit* attr, int64_t vcap,
@@ -175,9 +166,8 @@ int rm_sdf_mesh(rm_ctx* c, const rm_sdf_grid_desc* grid, uint32_t flags, float* 
   rmd::MeshArgs M;
   if ((rc = mesh_args(c, grid, &M)) != RM_OK) return rc;
   const rmd::Frame F = query_frame(c);
-  hipEvent_t e0, e1;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
+  Timed t;
+  if ((rc = t.begin(c)) != RM_OK) return rc;
   if ((rc = mesh_count(c, grid, F, M)) != RM_OK) return rc;
   // the call is synchronous: the host reads the counts and sizes the rest by them
   rm_sdf_mesh_counts n;
@@ -187,21 +177,21 @@ int rm_sdf_mesh(rm_ctx* c, const rm_sdf_grid_desc* grid, uint32_t flags, float* 
   const int64_t nq = (int64_t)n.quads < qcap ? (int64_t)n.quads : qcap;
   const size_t pb = (size_t)nv * 3 * sizeof(float), ab = attr ? (size_t)nv * sizeof(rm_ray_hit) : 0,
                ib = (size_t)nq * index_bytes(flags);
-  if ((rc = ensure_bytes(c, &c->d_sdf_in, &c->sdf_in_cap, pb, kBuffer)) != RM_OK) return rc;
-  if ((rc = ensure_bytes(c, &c->d_sdf_out, &c->sdf_out_cap, ab, kBuffer)) != RM_OK) return rc;
-  if ((rc = ensure_bytes(c, &c->d_mesh_idx, &c->mesh_idx_cap, ib, kBuffer)) != RM_OK) return rc;
-  M.pos = static_cast<float*>(c->d_sdf_in);
-  M.indices = static_cast<uint32_t*>(c->d_mesh_idx);
+  if ((rc = ensure(c, c->stage_in, pb, kBuffer)) != RM_OK) return rc;
+  if ((rc = ensure(c, c->stage_out, ab, kBuffer)) != RM_OK) return rc;
+  if ((rc = ensure(c, c->mesh_idx, ib, kBuffer)) != RM_OK) return rc;
+  M.pos = static_cast<float*>(c->stage_in.p);
+  M.indices = static_cast<uint32_t*>(c->mesh_idx.p);
   M.vcap = nv;
   M.qcap = nq;
   M.triangles = flags & RM_MESH_TRIANGLES;
   const hipError_t e = launch_mesh_emit(M, c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "sdf mesh: emit kernel launch");
-  if (ab && (rc = points_launch(c, F, c->d_sdf_in, nv, flags, c->d_sdf_out)) != RM_OK) return rc;
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
-  if (pb) RM_HIP(c, hipMemcpyAsync(pos, c->d_sdf_in, pb, hipMemcpyDeviceToHost, c->stream));
-  if (ab) RM_HIP(c, hipMemcpyAsync(attr, c->d_sdf_out, ab, hipMemcpyDeviceToHost, c->stream));
-  if (ib) RM_HIP(c, hipMemcpyAsync(indices, c->d_mesh_idx, ib, hipMemcpyDeviceToHost, c->stream));
+  if (ab && (rc = points_launch(c, F, c->stage_in.p, nv, flags, c->stage_out.p)) != RM_OK) return rc;
+  if ((rc = t.end(c)) != RM_OK) return rc;
+  if (pb) RM_HIP(c, hipMemcpyAsync(pos, c->stage_in.p, pb, hipMemcpyDeviceToHost, c->stream));
+  if (ab) RM_HIP(c, hipMemcpyAsync(attr, c->stage_out.p, ab, hipMemcpyDeviceToHost, c->stream));
+  if (ib) RM_HIP(c, hipMemcpyAsync(indices, c->mesh_idx.p, ib, hipMemcpyDeviceToHost, c->stream));
   RM_HIP(c, hipStreamSynchronize(c->stream));
   *counts = n;
   return RM_OK;

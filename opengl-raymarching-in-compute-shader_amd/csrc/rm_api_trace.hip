@@ -4,7 +4,6 @@
 // k_table_trace (a runtime scene table, rm_table_trace.hip).  DESIGN.md §4.9.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "rm_ctx.hpp"
@@ -19,7 +18,8 @@ constexpr uint32_t kAllFlags = RM_TRACE_REFLECTED | RM_TRACE_NORMAL | RM_TRACE_S
 
 // What every entry point refuses, before any device call.
 int check_query(rm_ctx* c, const void* origins, const void* dirs, int64_t n, uint32_t flags, const void* hits) {
-  if (!c->subs.empty()) return fail(c, RM_ERR_STATE, "ray queries: not available on a multi-device context (cfg.ngpus)");
+  const int rc = refuse_multi(c, "ray queries");
+  if (rc != RM_OK) return rc;
   if (n < 0 || n > INT32_MAX) return fail(c, RM_ERR_INVALID, "ray queries: n must be in 0..2^31 - 1");
   if (flags & ~kAllFlags) return fail(c, RM_ERR_INVALID, "ray queries: unknown flag bits");
   if ((flags & RM_TRACE_SHADOW) && flags != RM_TRACE_SHADOW)
@@ -31,50 +31,19 @@ int check_query(rm_ctx* c, const void* origins, const void* dirs, int64_t n, uin
 }
 
 // The trace kernel for the context's scene on its stream, after whatever is
-// queued there; n >= 1, device pointers.  The frame constants are a dispatch's
-// but for the two facts that hold for a frame's primary rays only: step 0 at
-// the camera (prepv) and |rd| = 1 (unit_rd).  The images and counters in F are
-// not touched by the trace kernels.
+// queued there; n >= 1, device pointers.
 int trace_launch(rm_ctx* c, const void* origins, const void* dirs, int64_t n, uint32_t flags, void* hits) {
   if (c->comm_failed) return comm_dead(c);
-  rmd::Frame F = make_frame(c);
-  std::memset(F.prepv, 0, sizeof F.prepv);
-  F.unit_rd = 0;
-  hipEvent_t e0, e1;
+  const rmd::Frame F = query_frame(c);
+  Timed t;
   int rc;
-  if ((rc = timing_events(c, &e0, &e1)) != RM_OK) return rc;
-  if (e0) RM_HIP(c, hipEventRecord(e0, c->stream));
-  // built-in or table code, as pick_kernel chooses for frames; a table always
-  // with the generic kernel (its specialised kernels render frames only)
-  const hipError_t e = c->nprims ? launch_table_trace(F, origins, dirs, hits, n, flags, c->stream)
-                                 : launch_trace(F, origins, dirs, hits, n, flags, c->stream);
+  if ((rc = t.begin(c)) != RM_OK) return rc;
+  const hipError_t e = scene_kernels(c).trace(F, origins, dirs, hits, n, flags, c->stream);
   if (e != hipSuccess) return hip_fail(c, e, "trace kernel launch");
-  if (e1) RM_HIP(c, hipEventRecord(e1, c->stream));
-  return RM_OK;
+  return t.end(c);
 }
 
-int ensure_staging(rm_ctx* c, int64_t n) {
-  if (n <= c->trace_cap) return RM_OK;
-  // a buffer in use by an earlier query is free once the stream has passed it: the
-  // host path is synchronous, so nothing of it is pending here
-  if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
-  if (c->d_trace_hits) (void)hipFree(c->d_trace_hits);
-  c->d_trace_rays = nullptr;
-  c->d_trace_hits = nullptr;
-  c->trace_cap = 0;
-  int64_t cap = 1024;
-  while (cap < n) cap *= 2;
-  if (hipMalloc(&c->d_trace_rays, (size_t)cap * 6 * sizeof(float)) != hipSuccess ||
-      hipMalloc(&c->d_trace_hits, (size_t)cap * sizeof(rm_ray_hit)) != hipSuccess) {
-    if (c->d_trace_rays) (void)hipFree(c->d_trace_rays);
-    c->d_trace_rays = nullptr;
-    c->d_trace_hits = nullptr;
-    (void)hipGetLastError();
-    return fail(c, RM_ERR_NOMEM, "ray queries: staging buffers for " + std::to_string(n) + " rays");
-  }
-  c->trace_cap = cap;
-  return RM_OK;
-}
+constexpr const char* kStaging = "ray queries: a staging buffer";
 
 }  // namespace
 
@@ -98,14 +67,16 @@ int rm_trace_rays(rm_ctx* c, const float* origins, const float* dirs, int64_t n,
   if (rc != RM_OK) return rc;
   if (n == 0) return RM_OK;
   if ((rc = set_device(c)) != RM_OK) return rc;
-  if ((rc = ensure_staging(c, n)) != RM_OK) return rc;
-  float* d_o = c->d_trace_rays;
-  float* d_d = c->d_trace_rays + 3 * c->trace_cap;
-  const size_t rb = (size_t)n * 3 * sizeof(float);
+  // the origins at the start of the shared input buffer, the dirs behind them at a 256-byte boundary
+  const size_t rb = (size_t)n * 3 * sizeof(float), doff = (rb + 255) / 256 * 256, hb = (size_t)n * sizeof(rm_ray_hit);
+  if ((rc = ensure(c, c->stage_in, doff + rb, kStaging)) != RM_OK) return rc;
+  if ((rc = ensure(c, c->stage_out, hb, kStaging)) != RM_OK) return rc;
+  void* const d_o = c->stage_in.p;
+  void* const d_d = static_cast<char*>(d_o) + doff;
   RM_HIP(c, hipMemcpyAsync(d_o, origins, rb, hipMemcpyHostToDevice, c->stream));
   RM_HIP(c, hipMemcpyAsync(d_d, dirs, rb, hipMemcpyHostToDevice, c->stream));
-  if ((rc = trace_launch(c, d_o, d_d, n, flags, c->d_trace_hits)) != RM_OK) return rc;
-  RM_HIP(c, hipMemcpyAsync(hits, c->d_trace_hits, (size_t)n * sizeof(rm_ray_hit), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = trace_launch(c, d_o, d_d, n, flags, c->stage_out.p)) != RM_OK) return rc;
+  RM_HIP(c, hipMemcpyAsync(hits, c->stage_out.p, hb, hipMemcpyDeviceToHost, c->stream));
   RM_HIP(c, hipStreamSynchronize(c->stream));
   return RM_OK;
 }

@@ -2,8 +2,9 @@
 // rm_api.hip (context, uniforms, dispatch, readback, timing, interop),
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
 // rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
-// rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling) and
-// rm_api_mesh.hip (SDF mesh extraction).
+// rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling),
+// rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
+// families share: their frame constants, checks and staging buffers).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
 
@@ -94,6 +95,21 @@ struct RenderKernel {
   bool takes_batch(bool counters) const { return table && !counters; }
 };
 
+// The kernels that are not frame kernels, for the built-in scene or for a runtime
+// scene table (rm_api.hip scene_kernels): the launch wrappers above.
+struct SceneKernels {
+  decltype(launch_trace)* trace;
+  decltype(launch_sdf_points)* sdf_points;
+  decltype(launch_sdf_grid)* sdf_grid;
+  decltype(launch_adapt_refine)* adapt_refine;
+};
+
+// A device buffer the context owns and grows on demand (rm_api_query.hip ensure).
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes
+};
+
 }  // namespace rm
 
 // The graph path: the captured frame (the render kernel, and for a rank of an
@@ -181,15 +197,12 @@ struct rm_ctx {
   hipEvent_t gdone = nullptr;       // the last batch's work on gstream
   hipEvent_t out_ev = nullptr;      // rm_wait_output: the tail of the context's stream
   bool gdone_pending = false;       // plain dispatches order after it
-  // rm_trace_rays' staging buffers, grown on demand: [cap] origins then [cap] dirs; [cap] rm_ray_hit
-  float* d_trace_rays = nullptr;
-  void* d_trace_hits = nullptr;
-  int64_t trace_cap = 0;
-  // rm_sdf_points' / rm_sdf_grid's staging buffers, grown on demand (bytes): the points, or a
-  // grid's ids; the records, or a grid's distances
-  void* d_sdf_in = nullptr;
-  void* d_sdf_out = nullptr;
-  size_t sdf_in_cap = 0, sdf_out_cap = 0;
+  // The staging buffers of the query families' host paths, which are synchronous: neither
+  // is live once a call returns, so the three families share them.  rm_trace_rays: the
+  // origins, and the dirs behind them at a 256-byte boundary; the hits.  rm_sdf_points: the
+  // points; the records.  rm_sdf_grid: the ids; the distances.  rm_sdf_mesh: the positions;
+  // the records.
+  rm::DevBuf stage_in, stage_out;
   // adaptive supersampling (rm_api_adaptive.hip), allocated on first use: the 0/1 mask
   // [height][width], the flagged pixels' list [height * width], the 8x8 tiles' counts and
   // offsets (whole scan chunks, rm_adaptive_args.hpp) and the total
@@ -201,14 +214,10 @@ struct rm_ctx {
   bool aa_dispatched = false;  // the mask and the total are those of a dispatch
   int aa_waves_env = 0;        // RM_AA_REFINE_WAVES at rm_create (0: unset)
   int aa_cus = 0;              // the device's compute units (first adaptive dispatch)
-  // SDF mesh extraction (rm_api_mesh.hip), grown on demand (bytes): the distance volume; the
-  // counts and the per-wave arrays (rm_mesh_args.hpp); rm_sdf_mesh's staging of the indices
-  // (its positions and records use d_sdf_in / d_sdf_out); rm_sdf_mesh_device's of the records
-  void* d_mesh_vol = nullptr;
-  void* d_mesh_waves = nullptr;
-  void* d_mesh_idx = nullptr;
-  void* d_mesh_attr = nullptr;
-  size_t mesh_vol_cap = 0, mesh_waves_cap = 0, mesh_idx_cap = 0, mesh_attr_cap = 0;
+  // SDF mesh extraction (rm_api_mesh.hip): the distance volume; the counts and the per-wave
+  // arrays (rm_mesh_args.hpp); rm_sdf_mesh's staging of the indices; rm_sdf_mesh_device's of
+  // the records
+  rm::DevBuf mesh_vol, mesh_waves, mesh_idx, mesh_attr;
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;
@@ -289,11 +298,20 @@ int check_uniforms(rm_ctx* c, const rm_uniforms& u);
 int create_fail(rm_ctx* c, int code);
 rmd::Frame make_frame(const rm_ctx* c);
 RenderKernel pick_kernel(const rm_ctx* c, const rmd::Frame& F);
+const SceneKernels& scene_kernels(const rm_ctx* c);
 // One frame, with or without counters (gbuf: the G-buffer image of a k.gbuf
 // kernel); the frames B.f[0..n) of one RenderKernel.
 hipError_t launch(const RenderKernel& k, const rmd::Frame& F, bool counters, hipStream_t s, void* gbuf = nullptr);
 hipError_t launch(const RenderKernel& k, const rmd::FrameBatch& B, int n, hipStream_t s);
-int timing_events(rm_ctx* c, hipEvent_t* e0, hipEvent_t* e1);
+// The bracket of a timed launch (rm_enable_timing; nothing with timing off): begin records
+// the first event of the context's next pair on its stream, end the second, and only end
+// claims the pair, with the frames the launch rendered.  A call that fails in between
+// leaves the pool as it found it.  Brackets do not nest on one context.
+struct Timed {
+  bool on = false;
+  int begin(rm_ctx* c);
+  int end(rm_ctx* c, int frames = 1);
+};
 int order_after_batch(rm_ctx* c);
 int render_launch(rm_ctx* c);
 int phase(rm_ctx* c, int k, hipStream_t st = nullptr);
@@ -314,15 +332,20 @@ int comm_assemble(rm_ctx* c);
 int multi_frame(rm_ctx* c, bool graph);
 int comm_batch(rm_ctx* c, const rm_uniforms* u, int n);
 
-// ---- rm_api_sdf.hip: what the field queries share with the mesh extraction (rm_api_mesh.hip) ----
+// ---- rm_api_query.hip: what the ray queries, the field queries and the mesh extraction share ----
 // The query's frame constants: a dispatch's, without the two facts about a frame's primary rays.
 rmd::Frame query_frame(const rm_ctx* c);
+// RM_ERR_STATE on a multi-device context; `who` names the family in the message.
+int refuse_multi(rm_ctx* c, const char* who);
+// The check of a grid descriptor (not null): every dim in 0..2^24, at most 2^31 - 1 points.
+// *total: the grid's points.  `who` starts the messages.
+int grid_points(rm_ctx* c, const char* who, const rm_sdf_grid_desc* g, int64_t* total);
 // The grid kernels' arguments for a grid of dims >= 1 and device outputs (4-byte aligned, one
 // of them possibly null): the lane mapping is chosen from nx and the outputs' alignment.
 rmd::SdfGridArgs sdf_grid_args(const rm_sdf_grid_desc* g, void* dist, void* ids);
-// A context-owned device buffer of at least `need` bytes, replaced when too small (hipFree
-// waits for the device, so nothing pending uses the old one); `what` names it in RM_ERR_NOMEM.
-int ensure_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need, const char* what);
+// b of at least `need` bytes, replaced when too small (hipFree waits for the device, so
+// nothing pending uses the old one); `what` names it in RM_ERR_NOMEM.
+int ensure(rm_ctx* c, DevBuf& b, size_t need, const char* what);
 
 // ---- rm_api_graph.hip: hipGraph replay -----------------------------------------------------
 void graph_release(rm_ctx* c);

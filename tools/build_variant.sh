@@ -21,9 +21,8 @@ fi
 pkg=opengl-raymarching-in-compute-shader_amd
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -I$src/include $*"
 b=$(mktemp -d)
-/opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/rm_api.hip" -o "$b/rm_api.o" &
-for f in rm_api_comm rm_api_graph rm_frame_math rm_api_trace rm_api_gbuffer rm_api_sdf rm_api_adaptive; do  # the C-ABI's other files (absent in older revisions)
-  [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
+for f in "$src/$pkg"/csrc/rm_api*.hip "$src/$pkg/csrc/rm_frame_math.hip"; do  # the C-ABI's files, whichever the revision has
+  [ -f "$f" ] && { /opt/rocm/bin/hipcc $flags -c "$f" -o "$b/$(basename "$f" .hip).o" & }
 done
 /opt/rocm/bin/hipcc $flags -fno-slp-vectorize -c "$src/$pkg/csrc/rm_table.hip" -o "$b/rm_table.o" &
 # rm_kernels.hip as the Makefile builds it (both objects without SLP; RM_PIXEL_SLP=1
@@ -35,9 +34,9 @@ case "$*" in
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} $pslp -DRM_KERNELS_PIXEL_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" &
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
 esac
-# the ray-query, G-buffer, SDF-query and adaptive kernels, as the Makefile builds them
+# the ray-query, G-buffer, SDF-query, adaptive and mesh kernels, as the Makefile builds them
 # (absent in older revisions)
-for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges; do
+for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges rm_mesh; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
 for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive; do
