@@ -23,16 +23,14 @@ LIBRM    := $(PKG)/librm.so
 ORACLE   := oracle/_build/librm_oracle.so
 DRIVER   := $(PKG)/rm_frameloop
 
-RM_SRCS  := $(CSRC)/rm_api.hip $(CSRC)/rm_api_comm.hip $(CSRC)/rm_api_graph.hip $(CSRC)/rm_frame_math.hip \
-            $(CSRC)/rm_kernels.hip $(CSRC)/rm_table.hip $(CSRC)/rm_jit.hip $(CSRC)/rm_host.cpp $(CSRC)/rm_comm.cpp \
-            $(CSRC)/rm_api_trace.hip $(CSRC)/rm_trace.hip $(CSRC)/rm_table_trace.hip \
-            $(CSRC)/rm_api_gbuffer.hip $(CSRC)/rm_gbuffer.hip $(CSRC)/rm_table_gbuffer.hip \
-            $(CSRC)/rm_api_sdf.hip $(CSRC)/rm_sdf.hip $(CSRC)/rm_table_sdf.hip \
-            $(CSRC)/rm_api_adaptive.hip $(CSRC)/rm_adaptive.hip $(CSRC)/rm_table_adaptive.hip \
-            $(CSRC)/rm_adaptive_edges.hip \
-            $(CSRC)/rm_api_mesh.hip $(CSRC)/rm_mesh.hip $(CSRC)/rm_api_query.hip
+# librm's objects, in link order: the link line and the sanitizer build's objects
+# come from this one list.
+RM_OBJS  := rm_api rm_api_comm rm_api_graph rm_frame_math rm_kernels rm_kernels_aa rm_table rm_jit rm_host rm_comm \
+            rm_api_trace rm_trace rm_table_trace rm_api_gbuffer rm_gbuffer rm_table_gbuffer \
+            rm_api_sdf rm_sdf rm_table_sdf rm_api_adaptive rm_adaptive rm_table_adaptive rm_adaptive_edges \
+            rm_api_mesh rm_mesh rm_api_query
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
-            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
+            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_builtin_fast.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
             $(CSRC)/rm_mesh_args.hpp \
             include/rm_api.h Makefile
 # The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
@@ -74,69 +72,30 @@ $(PKG)/build/rm_table.o: $(CSRC)/rm_table.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-# The ray-query kernels (rm_trace_rays) in objects of their own: each
-# includes the render kernels' source for its device code alone, with that
-# source's flags, and leaves rm_kernels.o / rm_kernels_aa.o / rm_table.o as they
-# are without it.
-$(PKG)/build/rm_trace.o: $(CSRC)/rm_trace.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
+# The query and output families in objects of their own, so
+# that rm_kernels.o / rm_kernels_aa.o / rm_table.o are what they are without
+# them.  The built-in scene's (ray queries, the G-buffer frame kernels, SDF field
+# queries, adaptive supersampling) include the render kernels' source for its
+# device code alone and take that source's flags; the scene-independent ones
+# (the geometry-edge classifier, mesh extraction) take the same flags.
+BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive
+PLAIN_FAMS   := rm_adaptive_edges rm_mesh
+$(BUILTIN_FAMS:%=$(PKG)/build/%.o): $(CSRC)/rm_kernels.hip
+$(BUILTIN_FAMS:%=$(PKG)/build/%.o) $(PLAIN_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(KFLAGS) -c $< -o $@
 
-# k_table_trace holds the table march twice over (the fast lanes' and the literal
-# path's): past the AMDGPU inliner's default cap on a caller's basic blocks (1100)
-# tmarch stays a call, and a call takes the staged Table and its result through
-# scratch memory (432 B per lane; none with the cap raised).
+# The scene-table halves include rm_table.hip in the same way, with rm_table.o's
+# flags and one more: k_table_trace holds the table march twice over (the fast
+# lanes' and the literal path's): past the AMDGPU inliner's default cap on a
+# caller's basic blocks (1100) tmarch stays a call, and a call takes the staged
+# Table and its result through scratch memory (432 B per lane; none with the cap
+# raised).
 TRACE_INLINE := -mllvm -amdgpu-inline-max-bb=8000
-$(PKG)/build/rm_table_trace.o: $(CSRC)/rm_table_trace.hip $(CSRC)/rm_table.hip $(RM_HDRS)
+TABLE_FAMS   := rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive
+$(TABLE_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(CSRC)/rm_table.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
-
-# The G-buffer frame kernels (RM_OUT_GBUFFER), in objects of their
-# own in the same way and with the same flags: the render kernels' device code
-# with one more sink for the primary hit.
-$(PKG)/build/rm_gbuffer.o: $(CSRC)/rm_gbuffer.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
-
-$(PKG)/build/rm_table_gbuffer.o: $(CSRC)/rm_table_gbuffer.hip $(CSRC)/rm_table.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
-
-# The SDF field-query kernels (rm_sdf_points / rm_sdf_grid), in
-# objects of their own in the same way: rm_sdf.o with the render kernels' flags,
-# rm_table_sdf.o with rm_table_trace.o's.
-$(PKG)/build/rm_sdf.o: $(CSRC)/rm_sdf.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
-
-$(PKG)/build/rm_table_sdf.o: $(CSRC)/rm_table_sdf.hip $(CSRC)/rm_table.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
-
-# The adaptive-supersampling kernels (rm_dispatch_adaptive / rm_dispatch_refine,
-# DESIGN §4.12), in objects of their own in the same way: rm_adaptive.o with
-# rm_gbuffer.o's flags, rm_table_adaptive.o with rm_table_gbuffer.o's.
-$(PKG)/build/rm_adaptive.o: $(CSRC)/rm_adaptive.hip $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
-
-$(PKG)/build/rm_table_adaptive.o: $(CSRC)/rm_table_adaptive.hip $(CSRC)/rm_table.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
-
-# k_adapt_classify_edges (rm_dispatch_adaptive_edges): scene
-# independent, in an object of its own with rm_adaptive.o's flags, so that
-# rm_adaptive.o's kernels are what they were without it.
-$(PKG)/build/rm_adaptive_edges.o: $(CSRC)/rm_adaptive_edges.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
-
-# The mesh-extraction kernels (rm_sdf_mesh): scene independent, in
-# an object of their own with rm_adaptive_edges.o's flags; the volume and the
-# attributes come from rm_sdf.o's / rm_table_sdf.o's kernels, unchanged.
-$(PKG)/build/rm_mesh.o: $(CSRC)/rm_mesh.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
 
 $(PKG)/build/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
 	@mkdir -p $(dir $@)
@@ -155,14 +114,7 @@ $(PKG)/build/rm_comm.o: $(CSRC)/rm_comm.cpp $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-$(LIBRM): $(PKG)/build/rm_api.o $(PKG)/build/rm_api_comm.o $(PKG)/build/rm_api_graph.o $(PKG)/build/rm_frame_math.o \
-          $(PKG)/build/rm_kernels.o $(PKG)/build/rm_kernels_aa.o $(PKG)/build/rm_table.o $(PKG)/build/rm_jit.o $(PKG)/build/rm_host.o $(PKG)/build/rm_comm.o \
-          $(PKG)/build/rm_api_trace.o $(PKG)/build/rm_trace.o $(PKG)/build/rm_table_trace.o \
-          $(PKG)/build/rm_api_gbuffer.o $(PKG)/build/rm_gbuffer.o $(PKG)/build/rm_table_gbuffer.o \
-          $(PKG)/build/rm_api_sdf.o $(PKG)/build/rm_sdf.o $(PKG)/build/rm_table_sdf.o \
-          $(PKG)/build/rm_api_adaptive.o $(PKG)/build/rm_adaptive.o $(PKG)/build/rm_table_adaptive.o \
-          $(PKG)/build/rm_adaptive_edges.o \
-          $(PKG)/build/rm_api_mesh.o $(PKG)/build/rm_mesh.o $(PKG)/build/rm_api_query.o
+$(LIBRM): $(RM_OBJS:%=$(PKG)/build/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
@@ -233,23 +185,11 @@ ASANORC  := oracle/_build/librm_oracle_asan.so
 SANHOST  := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
             -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer
-ASAN_OBJS := $(addprefix $(ASAN_DIR)/,rm_api.o rm_api_comm.o rm_api_graph.o rm_frame_math.o rm_kernels.o rm_kernels_aa.o rm_table.o rm_jit.o rm_host.o rm_comm.o \
-                                      rm_api_trace.o rm_trace.o rm_table_trace.o \
-                                      rm_api_gbuffer.o rm_gbuffer.o rm_table_gbuffer.o \
-                                      rm_api_sdf.o rm_sdf.o rm_table_sdf.o \
-                                      rm_api_adaptive.o rm_adaptive.o rm_table_adaptive.o \
-                                      rm_adaptive_edges.o \
-                                      rm_api_mesh.o rm_mesh.o rm_api_query.o)
+ASAN_OBJS := $(RM_OBJS:%=$(ASAN_DIR)/%.o)
 asan: $(ASANLIB) $(ASANORC)
 
-$(ASAN_DIR)/rm_trace.o: $(CSRC)/rm_kernels.hip
-$(ASAN_DIR)/rm_table_trace.o: $(CSRC)/rm_table.hip
-$(ASAN_DIR)/rm_gbuffer.o: $(CSRC)/rm_kernels.hip
-$(ASAN_DIR)/rm_table_gbuffer.o: $(CSRC)/rm_table.hip
-$(ASAN_DIR)/rm_sdf.o: $(CSRC)/rm_kernels.hip
-$(ASAN_DIR)/rm_table_sdf.o: $(CSRC)/rm_table.hip
-$(ASAN_DIR)/rm_adaptive.o: $(CSRC)/rm_kernels.hip
-$(ASAN_DIR)/rm_table_adaptive.o: $(CSRC)/rm_table.hip
+$(BUILTIN_FAMS:%=$(ASAN_DIR)/%.o): $(CSRC)/rm_kernels.hip
+$(TABLE_FAMS:%=$(ASAN_DIR)/%.o): $(CSRC)/rm_table.hip
 $(ASAN_DIR)/%.o: $(CSRC)/%.hip $(RM_HDRS) $(PKG)/build/rm_jit_src.inc
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -I$(PKG)/build -c $< -o $@

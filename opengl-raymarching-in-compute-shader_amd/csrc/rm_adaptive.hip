@@ -129,14 +129,6 @@ __global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_scatter(AdaptArgs A)
   A.list[at] = (uint32_t)px | ((uint32_t)py << 16);  // both <= 65535
 }
 
-// The lane id re-formed after the march (rm_table.hip out_lane): the list entry is
-// read again from it instead of px, py staying live across render<>.
-__device__ __forceinline__ int adapt_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
 // The frame constants as k_sample_frames takes them (a batch of one): a round
 // reads the fields it needs from the kernel arguments at an index the compiler
 // cannot see through, as that kernel reads its frame's, so they are scalar loads
@@ -156,6 +148,10 @@ __global__ __launch_bounds__(64, 8) void k_adapt_refine(AdaptFrame B, AdaptArgs 
     int slot = 0;
     asm volatile("" : "+s"(slot));
     const Frame& F = B.f[slot];
+    // The round in this kernel's own text, not adapt_refine_round over BuiltinFast
+    // (rm_adaptive_args.hpp, k_table_adapt_refine's): that form's code object differed
+    // from this one's in the operand order of two integer adds, and the A/B of the two
+    // (profiles/fast_scene_ab.txt) had one figure above this one's spread in most runs.
     // the group's entries: 16, or what is left of the list (indices below 2^32)
     const uint32_t* __restrict__ ent = A.list + g * 16ull;
     const unsigned long long left = total - g * 16ull;

@@ -1,11 +1,14 @@
 // rm_adaptive_args.hpp — the kernel arguments of adaptive supersampling
 // (rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine, DESIGN.md
 // §4.12), shared by the kernels (rm_adaptive.hip, rm_adaptive_edges.hip,
-// rm_table_adaptive.hip) and the host (rm_api_adaptive.hip).
+// rm_table_adaptive.hip) and the host (rm_api_adaptive.hip), the refine kernels'
+// lane helper (adapt_lane) and their round over Fast (adapt_refine_round).
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+
+#include "rm_scene.hpp"
 
 namespace rmd {
 
@@ -36,5 +39,50 @@ struct EdgeArgs {
   int32_t color_threshold;
   float depth_rel, normal_cos;
 };
+
+// The lane id re-formed after the march (rm_table.hip out_lane): the list entry is
+// read again from it instead of px, py staying live across the render.
+__device__ __forceinline__ int adapt_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// One round of a refine kernel: group g of 16 list entries x 4 samples on one
+// wave, over the fast-path scene sc (Fast, rm_trace.hpp): cast_ray, render, the
+// three-shuffle sum and store_pixel of the AA kernels' sample bodies in the same
+// order, so a refined pixel is the AA-on frame's bit for bit.  k_table_adapt_refine
+// calls it over TableFast; k_adapt_refine (rm_adaptive.hip) holds the same round in
+// its own text for now (see there).
+template <class Fast>
+__device__ __forceinline__ void adapt_refine_round(const Frame& F, const AdaptArgs& A, unsigned long long total,
+                                                   unsigned long long g, const Fast& sc) {
+  // the group's entries: 16, or what is left of the list (indices below 2^32)
+  const uint32_t* __restrict__ ent = A.list + g * 16ull;
+  const unsigned long long left = total - g * 16ull;
+  const int n = left < 16ull ? (int)left : 16;
+  // entry q = lane >> 2 of the group, sample s = lane & 3: as sample_body's lanes.
+  // The spare lanes of a partial last group stay idle (all 4 of a pixel together).
+  f3 col = mk(0.0f, 0.0f, 0.0f);
+  {
+    const int lane = threadIdx.x & 63;
+    if ((lane >> 2) < n) {
+      const uint32_t e = ent[lane >> 2];
+      f3 ro, rd;
+      cast_ray(F, lane_uv(F, 0, (int)(e & 0xffffu), lane & 3), lane_uv(F, 1, (int)(e >> 16), lane & 3), ro, rd);
+      col = sc.render(ro, rd);
+    }
+  }
+  const int ol = adapt_lane();
+  const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
+  const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
+  const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+  if ((ol & 3) == 0 && (ol >> 2) < n) {
+    const uint32_t e = ent[ol >> 2];
+    const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
+    const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3, o2 = ((col.z + b1) + b2) + b3;
+    store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+  }
+}
 
 }  // namespace rmd

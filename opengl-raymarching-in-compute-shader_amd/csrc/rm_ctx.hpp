@@ -27,6 +27,11 @@ static_assert(RM_MAX_BATCH == rmd::kMaxBatch, "rm_api.h RM_MAX_BATCH == rm_scene
 namespace rm {
 
 // ---- the kernels' launch wrappers (rm_kernels.hip, rm_table.hip) ---------------------
+// A query family (rays, SDF fields, adaptive refinement) is one body in its header
+// (rm_trace.hpp, rm_sdf.hpp, rm_adaptive_args.hpp) over the fast-path scene interface
+// (Fast, rm_trace.hpp: BuiltinFast in rm_builtin_fast.hpp, TableFast in rm_table_lit.hpp)
+// and the literal path's (Scene: BuiltinLit, TableLit), and per scene a translation
+// unit with the kernel that calls the body and the launch wrapper below.
 void pixel_grid(int width, int rows, bool aa, int32_t* gx, int32_t* gy);
 hipError_t launch_pixel(const rmd::Frame& F, bool counters, hipStream_t s);
 hipError_t launch_table(const rmd::Frame& F, bool counters, hipStream_t s, int nslots, int shape);

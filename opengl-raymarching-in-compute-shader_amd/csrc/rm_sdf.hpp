@@ -1,10 +1,11 @@
 // rm_sdf.hpp — SDF field queries (rm_sdf_points, rm_sdf_grid; include/rm_api.h):
-// what the four kernels share.  k_sdf_points / k_sdf_grid (rm_sdf.hip, the
-// built-in scene) and k_table_sdf_points / k_table_sdf_grid (rm_table_sdf.hip,
-// runtime scene tables) evaluate sdf(p) (glsl:107-123) and GetNormal(p)
-// (glsl:278-288) at caller-supplied points or on a regular grid, one point per
-// lane in one-wave workgroups, with the render kernels' exact evaluations
-// (scene_cull / normal_samples, Table::dist / tnormal).
+// the four kernels' bodies, written once over Fast and Scene (rm_trace.hpp).
+// k_sdf_points / k_sdf_grid (rm_sdf.hip, the built-in scene) and
+// k_table_sdf_points / k_table_sdf_grid (rm_table_sdf.hip, runtime scene tables)
+// evaluate sdf(p) (glsl:107-123) and GetNormal(p) (glsl:278-288) at
+// caller-supplied points or on a regular grid, one point per lane in one-wave
+// workgroups, with the render kernels' exact evaluations (Fast's dist / attrs /
+// field_normal: scene_cull / normal_samples, Table::dist / tnormal).
 //
 // Those evaluations cull with bounds stated for finite points whose squares stay
 // far from overflow.  sdf_fast_ok() is the predicate under which they hold
@@ -51,6 +52,42 @@ __device__ __forceinline__ TraceRec lit_sdf(const Scene& sc, f3 p, uint32_t flag
   return r;
 }
 
+// The point kernels' body: one point per lane, 64 consecutive points per
+// one-wave workgroup; the flags are uniform.
+template <class Fast, class Lit>
+__device__ __forceinline__ void sdf_points_body(const SdfPointArgs& A, const Fast& fast, const Lit& lit) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  const f3 p = trace_load3(A.points, i);
+  const uint32_t flags = A.flags;
+  const bool ok = sdf_fast_ok(p);
+  TraceRec r = sdf_rec();
+  if (ok) {
+    int k;
+    r.t = fast.dist(p, k);
+    fast.attrs(k, p, r.id, r.material, r.albedo);
+    if (flags & RM_SDF_NORMAL) r.normal = fast.field_normal(p, r.t);
+  }
+  // the lanes outside the predicate, after the fast ones
+  if (!ok) r = lit_sdf(lit, p, flags);
+  sdf_store(A.out, i, r);
+}
+
+// The grid kernels' evaluation of one point: the distance, and the id of its opU winner.
+template <class Fast, class Lit>
+struct SdfGridEval {
+  Fast fast;
+  Lit lit;
+  __device__ __forceinline__ SdfGridEval(const Fast& f, const Lit& l) : fast(f), lit(l) {}
+  __device__ __forceinline__ void operator()(f3 p, float& d, int& id) const {
+    const bool ok = sdf_fast_ok(p);
+    int k = 0;
+    if (ok) d = fast.dist(p, k);
+    if (!ok) d = lit.dist(p, k);
+    id = lit.id(k);
+  }
+};
+
 // The grid kernels' body around one evaluation `eval(p, d, id)`: the wave's
 // (row, x-block) pairs, G.nwg of them taken with a grid stride (the launch holds
 // at most kSdfGridMaxWg workgroups: a dispatch counts work-items in 32 bits, so
@@ -92,6 +129,22 @@ __device__ __forceinline__ void sdf_grid_body(const SdfGridArgs& G, Eval eval) {
       }
     }
   }
+}
+
+// The launch wrappers' packing; lds is the kernel's dynamic LDS bytes.
+// n >= 1 points; device pointers, out 16-byte aligned.
+inline hipError_t launch_sdf_points_kernel(void (*kernel)(Frame, SdfPointArgs), size_t lds, const Frame& F,
+                                           const void* points, void* out, int64_t n, uint32_t flags, hipStream_t s) {
+  const SdfPointArgs A{static_cast<const float*>(points), static_cast<float4*>(out), (int32_t)n, flags};
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, F, A);
+  return hipGetLastError();
+}
+// Every dim >= 1; min(G.nwg, kSdfGridMaxWg) workgroups, each taking its pairs with a grid stride.
+inline hipError_t launch_sdf_grid_kernel(void (*kernel)(Frame, SdfGridArgs), size_t lds, const Frame& F,
+                                         const SdfGridArgs& G, hipStream_t s) {
+  const unsigned blocks = G.nwg < kSdfGridMaxWg ? G.nwg : kSdfGridMaxWg;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, s, F, G);
+  return hipGetLastError();
 }
 
 }  // namespace rmd

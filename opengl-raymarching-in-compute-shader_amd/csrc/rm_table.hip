@@ -1520,7 +1520,25 @@ __global__ __launch_bounds__(64, SL ? RM_TABLE_SL_WAVES : RM_TABLE_MIN_WAVES) vo
 
 }  // namespace rmd
 
-// (RM_TABLE_DEVICE_ONLY: rm_table_trace.hip includes this file for the device code above alone)
+// The launch side.  hiprtc (RM_TABLE_STATIC) sees none of it; the families that
+// include this file for the device code above alone (RM_TABLE_DEVICE_ONLY:
+// rm_table_trace.hip, rm_table_gbuffer.hip, rm_table_sdf.hip, rm_table_adaptive.hip)
+// see the two helpers their own launch wrappers need.
+#ifndef RM_TABLE_STATIC
+namespace rm {
+// Dynamic LDS of a generic table kernel (stage): the table, then the lazy slots'
+// balls (Table::sb) on a 16-byte boundary.
+inline size_t table_lds_bytes(int nprims) {
+  return (((rm::scene_words(nprims) + 3) & ~(size_t)3) + 4 * (size_t)rm::EX_MAX_SLOTS) * sizeof(float);
+}
+// One-wave workgroups over n frames like F: 4x4 pixels x 4 samples under AA, else 8x8 pixels.
+inline dim3 table_tile_grid(const rmd::Frame& F, int n = 1) {
+  const int e = F.aa ? 4 : 8;
+  return dim3((F.width + e - 1) / e, (F.rows + e - 1) / e, n);
+}
+}  // namespace rm
+#endif
+
 #if !defined(RM_TABLE_STATIC) && !defined(RM_TABLE_DEVICE_ONLY)
 namespace rm {
 
@@ -1540,24 +1558,21 @@ void launch_table_kl(const rmd::Frame& F, bool counters, hipStream_t s) {
     launch_table_frames_kl<KL, SL>(B, 1, s);
     return;
   }
-  // the table, then the lazy slots' balls (Table::sb)
-  const size_t lds = (((rm::scene_words(F.nprims) + 3) & ~(size_t)3) + 4 * (size_t)rm::EX_MAX_SLOTS) * sizeof(float);
+  const size_t lds = table_lds_bytes(F.nprims);
   if (F.aa)
-    hipLaunchKernelGGL((rmd::k_table_sample<true, KL>), dim3((F.width + 3) / 4, (F.rows + 3) / 4), dim3(64), lds, s, F);
+    hipLaunchKernelGGL((rmd::k_table_sample<true, KL>), table_tile_grid(F), dim3(64), lds, s, F);
   else
-    hipLaunchKernelGGL((rmd::k_table_pixel<true, KL>), dim3((F.width + 7) / 8, (F.rows + 7) / 8), dim3(64), lds, s, F);
+    hipLaunchKernelGGL((rmd::k_table_pixel<true, KL>), table_tile_grid(F), dim3(64), lds, s, F);
 }
 
 template <int KL, int SL>
 void launch_table_frames_kl(const rmd::FrameBatch& B, int n, hipStream_t s) {
   const rmd::Frame& F = B.f[0];
-  const size_t lds = (((rm::scene_words(F.nprims) + 3) & ~(size_t)3) + 4 * (size_t)rm::EX_MAX_SLOTS) * sizeof(float);
+  const size_t lds = table_lds_bytes(F.nprims);
   if (F.aa)
-    hipLaunchKernelGGL((rmd::k_table_sample_frames<KL, SL>), dim3((F.width + 3) / 4, (F.rows + 3) / 4, n), dim3(64),
-                       lds, s, B);
+    hipLaunchKernelGGL((rmd::k_table_sample_frames<KL, SL>), table_tile_grid(F, n), dim3(64), lds, s, B);
   else
-    hipLaunchKernelGGL((rmd::k_table_pixel_frames<KL, SL>), dim3((F.width + 7) / 8, (F.rows + 7) / 8, n), dim3(64),
-                       lds, s, B);
+    hipLaunchKernelGGL((rmd::k_table_pixel_frames<KL, SL>), table_tile_grid(F, n), dim3(64), lds, s, B);
 }
 
 // The generic kernel's instance for a table: KL = TABLE_FEW_SLOTS or

@@ -36,12 +36,8 @@ namespace rm {
 // rows * width records.
 hipError_t launch_table_gbuf(const rmd::Frame& F, void* gbuf, hipStream_t s) {
   const rmd::GbufArgs A{static_cast<float4*>(gbuf)};
-  // the table, then the lazy slots' balls (Table::sb), as the render kernels stage them
-  const size_t lds = (((rm::scene_words(F.nprims) + 3) & ~(size_t)3) + 4 * (size_t)rm::EX_MAX_SLOTS) * sizeof(float);
-  if (F.aa)
-    hipLaunchKernelGGL(rmd::k_table_gbuf_sample, dim3((F.width + 3) / 4, (F.rows + 3) / 4), dim3(64), lds, s, F, A);
-  else
-    hipLaunchKernelGGL(rmd::k_table_gbuf_pixel, dim3((F.width + 7) / 8, (F.rows + 7) / 8), dim3(64), lds, s, F, A);
+  hipLaunchKernelGGL(F.aa ? rmd::k_table_gbuf_sample : rmd::k_table_gbuf_pixel, table_tile_grid(F), dim3(64),
+                     table_lds_bytes(F.nprims), s, F, A);
   return hipGetLastError();
 }
 

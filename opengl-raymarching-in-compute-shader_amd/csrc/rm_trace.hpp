@@ -1,8 +1,9 @@
-// rm_trace.hpp — ray queries (rm_trace_rays, include/rm_api.h): what the two
-// trace kernels share.  k_trace (rm_trace.hip, the built-in scene) and
-// k_table_trace (rm_table_trace.hip, runtime scene tables) march caller-supplied
-// rays, one ray per lane in one-wave workgroups, with the render kernels' device
-// code: march / get_normal / softshadow / render and their table forms.
+// rm_trace.hpp — ray queries (rm_trace_rays, include/rm_api.h): the two trace
+// kernels' body, written once over two scene interfaces.  k_trace (rm_trace.hip,
+// the built-in scene) and k_table_trace (rm_table_trace.hip, runtime scene
+// tables) march caller-supplied rays, one ray per lane in one-wave workgroups,
+// with the render kernels' device code: march / get_normal / softshadow / render
+// and their table forms, behind the fast-path interface (Fast, below).
 //
 // That code cuts work with proofs (lazy culling, the provable-miss, step-cap and
 // shadow exits: rm_scene.hpp, rm_table.hip) whose margins are stated for the
@@ -63,8 +64,32 @@ __device__ __forceinline__ void trace_store(float4* hits, int64_t i, const Trace
   o[2] = make_float4(r.normal.z, r.color.x, r.color.y, r.color.z);
 }
 
+// ---- the fast path ---------------------------------------------------------------------
+// What a query family calls on a lane inside its predicate: the render kernels'
+// device code, proofs and all, in the instantiations the adapters name.  Every
+// call holds its own work counter (Cnt / TCnt: no counting build).
+// Fast: FastHit march(f3 ro, f3 rd, bool reflected) const
+//       f3 normal(f3 pos, float d) const    GetNormal at a march's hit, d its last distance (the centre sample),
+//       float shadow(f3 ro, f3 rd) const    softshadow,
+//       f3 render(f3 ro, f3 rd) const       a primary ray's colour,
+//       float dist(f3 p, int& k) const, void attrs(int k, f3 p, int&, float&, f3&) const
+//                                           as Scene's below, for the points of sdf_fast_ok (rm_sdf.hpp),
+//       f3 field_normal(f3 p, float d) const   GetNormal at such a point, d = dist(p).
+// BuiltinFast (rm_builtin_fast.hpp, over rm_kernels.hip) and TableFast
+// (rm_table_lit.hpp, over rm_table.hip) implement it.  A new family writes its
+// body once over Fast and Scene in its header, and per scene a kernel that calls
+// the body and a launch wrapper.
+struct FastHit {
+  float t;  // -1: no hit
+  int id;
+  float material;
+  f3 color;
+  float d;  // a hit's last distance: sdf at the hit point itself
+};
+
 // ---- the literal path ------------------------------------------------------------------
 // Scene: float dist(f3 p, int& k) const   sdf(p).hitpoint and its opU winner k,
+//        int id(int k) const   the winner's id,
 //        void attrs(int k, f3 p, int&, float&, f3&) const   the winner's id, material, colour.
 struct LitHit {
   float t;
@@ -113,6 +138,7 @@ struct BuiltinLit {
     }
     return opu(d, dot(p, mk(0.0f, 1.0f, 0.0f)) + 5.5f, 7);                         // glsl:85,121
   }
+  __device__ __forceinline__ int id(int k) const { return k; }
   __device__ __forceinline__ void attrs(int k, f3 p, int& id, float& material, f3& color) const {
     id = k;
     material = k == 7 ? 0.0f : 1.0f;  // MATTE: the floor alone
@@ -257,6 +283,51 @@ __device__ __forceinline__ TraceRec lit_trace(const Frame& F, const Scene& sc, f
   if ((flags & RM_TRACE_NORMAL) && h.t != -1.0f) r.normal = lit_normal(sc, add(ro, muls(rd, h.t)));
   if (flags & RM_TRACE_SHADE) r.color = lit_render(F, sc, ro, rd, h);
   return r;
+}
+
+// ---- the kernels' body and launch --------------------------------------------------------
+// One ray per lane, 64 consecutive rays per one-wave workgroup; the flags are
+// uniform.  The query Frame has prepv[PREP_VALID] = 0 and unit_rd = 0
+// (rm_api_trace.hip): step 0 at the camera and |rd| = 1 are facts about a
+// frame's primary rays only.
+template <class Fast, class Lit>
+__device__ __forceinline__ void trace_body(const Frame& F, const TraceArgs& A, const Fast& fast, const Lit& lit) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.n) return;
+  const f3 ro = trace_load3(A.origins, i), rd = trace_load3(A.dirs, i);
+  const uint32_t flags = A.flags;
+  const bool ok = trace_fast_ok(ro, rd);
+  TraceRec r = trace_miss();
+  if (ok) {
+    if (flags & RM_TRACE_SHADOW) {
+      r.t = fast.shadow(ro, rd);
+      r.id = 0;
+      r.material = 0.0f;
+    } else {
+      const FastHit h = fast.march(ro, rd, (flags & RM_TRACE_REFLECTED) != 0);
+      r.t = h.t;
+      r.id = h.id;
+      r.material = h.material;
+      r.albedo = h.color;
+      // (the centre sample of the normal is the march's last distance: the same point)
+      if ((flags & RM_TRACE_NORMAL) && h.t != -1.0f) r.normal = fast.normal(add(ro, muls(rd, h.t)), h.d);
+      if (flags & RM_TRACE_SHADE) r.color = fast.render(ro, rd);
+    }
+  }
+  // the lanes outside the predicate, after the fast ones (no vote of theirs is shared)
+  if (!ok) r = lit_trace(F, lit, ro, rd, flags);
+  trace_store(A.hits, i, r);
+}
+
+// The launch wrappers' packing: n >= 1 rays; origins / dirs / hits are device
+// pointers, hits 16-byte aligned; lds the kernel's dynamic LDS bytes.
+inline hipError_t launch_trace_kernel(void (*kernel)(Frame, TraceArgs), size_t lds, const Frame& F,
+                                      const void* origins, const void* dirs, void* hits, int64_t n, uint32_t flags,
+                                      hipStream_t s) {
+  const TraceArgs A{static_cast<const float*>(origins), static_cast<const float*>(dirs), static_cast<float4*>(hits),
+                    (int32_t)n, flags};
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, s, F, A);
+  return hipGetLastError();
 }
 
 }  // namespace rmd
