@@ -30,6 +30,9 @@ struct BuiltinFast {
     Cnt c = {0, 0, 0, 0, 0, 0};
     return rmd::render<false>(F, ro, rd, c);
   }
+  // trace_fast_ok is the whole predicate: the floor bounds a shadow march's steps
+  // (DESIGN.md §4.9 item 3).
+  __device__ __forceinline__ bool shadow_ok(f3, f3) const { return true; }
   // sdf(p): value and opU id with bounding-ball culling.
   __device__ __forceinline__ float dist(f3 p, int& k) const { return scene_cull<true>(p, F.blend, F.omblend, k); }
   __device__ __forceinline__ void attrs(int k, f3 p, int& id, float& material, f3& color) const {

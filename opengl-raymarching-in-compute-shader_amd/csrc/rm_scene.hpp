@@ -985,8 +985,27 @@ __device__ __forceinline__ f3 point_light(const Frame& F, f3 color, f3 normal, f
   return mul(color, add(add(diffuse, ambient), specular));
 }
 
+#ifdef RM_QUERY_GAMMA
+// The gamma of the ray-query kernels (rm_trace.hip, rm_table_trace.hip define the
+// switch; no frame kernel does).  gpow's absolute error grows with its result:
+// log2 x and the product carry 1 and 1/2 ulp of their own size into the exponent,
+// and v_exp_f32 adds an ulp of the result.  For x <= 16 (a result <= 3.53) that is
+// below (0.4545 * 2^-22 + 2^-24) ln 2 + 2^-23 = 2.4e-7 relative, 8.4e-7 absolute,
+// inside DESIGN §5's 2e-6 with powf's own half ulp; a frame's unit rays stay far
+// below 16 and the two gammas are the same there, bit for bit.  A query's rd is
+// any length within 2^-12 .. 2^12 (and any at all on the literal path): its sky
+// term 0.6 - 0.2 rd.y reaches 800, and gpow would be 3e-6 to 8e-6 off there.
+// Above 16 the power is taken in double and rounded once.
+__device__ __forceinline__ float gamma_pow(float x) {
+  if (x > 16.0f) return (float)::exp2((double)0.4545f * ::log2((double)x));
+  return gpow(x, 0.4545f);
+}
+#else
+__device__ __forceinline__ float gamma_pow(float x) { return gpow(x, 0.4545f); }
+#endif
+
 __device__ __forceinline__ f3 gamma(f3 c) {
-  return mk(gpow(c.x, 0.4545f), gpow(c.y, 0.4545f), gpow(c.z, 0.4545f));
+  return mk(gamma_pow(c.x), gamma_pow(c.y), gamma_pow(c.z));
 }
 
 // uv of pixel column (axis 0) / row (axis 1) p, sample s (-1: no supersampling):

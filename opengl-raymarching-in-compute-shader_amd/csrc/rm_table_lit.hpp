@@ -55,6 +55,31 @@ struct TableFast {
     TCnt c = {0, 0, 0, 0, 0, 0};
     return trender<false, KL, 0>(F, S, ro, rd, c);
   }
+  // The table term of the predicate for RM_TRACE_SHADOW.
+  // softshadow has no escape test, and a table need not have the built-in floor
+  // that bounds its steps: along a ray that leaves every entry behind t grows
+  // geometrically, p(t) overflows within the 16 steps, and the GLSL's answer is
+  // then what inf and NaN distances make of it (a plane with a negative
+  // coefficient on the axis that overflows first: -inf, 0.05), where tshadow has
+  // left through table_exit_T with res.  Every entry's value is at most
+  // L (|p|_1 + 2 S) (L = EX_LIP >= 1, S = EX_S >= |c|_1 + the sum of the entry's
+  // |parameters|: a bounded entry is below |q| + S, a capsule |q - a| + |ba|, a plane
+  // |n| |q| + |w|), so a step is at most b + (g - 1) t with b = L (|ro|_1 + 2 S),
+  // g = 1 + L |rd|_1, t <= 16 b g^15 after 16 steps and |p|_1 <= 17 b g^16 / L.
+  // b g^17 <= 2^56 keeps |p|_1 below 2^61 (the float error of the values, 2^-12
+  // relative, is inside 17 < 32) and every square in an sdf finite, which is what
+  // the bounds of tshadow assume; past it the lane marches literally, 16 steps over
+  // every entry.  An overflow of the product is +inf and fails; a table without
+  // valid bounds fails too.
+  __device__ __forceinline__ bool shadow_ok(f3 ro, f3 rd) const {
+    const float* ex = S.exits();
+    if (ex[rm::EX_VALID] == 0.0f) return false;
+    const float ro1 = (fabsf(ro.x) + fabsf(ro.y)) + fabsf(ro.z);
+    const float rd1 = (fabsf(rd.x) + fabsf(rd.y)) + fabsf(rd.z);
+    const float g = 1.0f + ex[rm::EX_LIP] * rd1, b = ex[rm::EX_LIP] * (ro1 + 2.0f * ex[rm::EX_S]);
+    const float g2 = g * g, g4 = g2 * g2, g8 = g4 * g4;
+    return (g8 * g8) * g * b <= 0x1p56f;
+  }
   // Table::dist is the table's sdf with per-point culling; tnormal's centre
   // sample is that value at the same point, and its tnormalize is the IEEE
   // v * (1 / sqrt(dot)) over the whole float range already.

@@ -6,7 +6,8 @@
 // on traces through this generic, LDS-staged code too.  The device code is
 // rm_table.hip's (tmarch / tnormal / tshadow / trender over the staged Table),
 // included without its kernels' launch wrappers.  The kernel's text is trace_body
-// (rm_trace.hpp) over TableFast / TableLit.
+// (rm_trace.hpp) over TableFast / TableLit.  RM_QUERY_GAMMA: rm_scene.hpp gamma_pow.
+#define RM_QUERY_GAMMA
 #define RM_TABLE_DEVICE_ONLY
 #include "rm_table.hip"
 

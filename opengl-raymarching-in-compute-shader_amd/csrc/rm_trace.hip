@@ -6,7 +6,8 @@
 // code is rm_kernels.hip's, included with both of its *_ONLY switches set: that
 // leaves its templates (march, get_normal, softshadow, render) and drops every
 // kernel and launch wrapper of its own.  The kernel's text is trace_body
-// (rm_trace.hpp) over BuiltinFast / BuiltinLit.
+// (rm_trace.hpp) over BuiltinFast / BuiltinLit.  RM_QUERY_GAMMA: rm_scene.hpp gamma_pow.
+#define RM_QUERY_GAMMA
 #define RM_KERNELS_PIXEL_ONLY
 #define RM_KERNELS_AA_ONLY
 #include "rm_kernels.hip"

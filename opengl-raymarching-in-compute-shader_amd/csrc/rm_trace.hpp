@@ -71,6 +71,7 @@ __device__ __forceinline__ void trace_store(float4* hits, int64_t i, const Trace
 // Fast: FastHit march(f3 ro, f3 rd, bool reflected) const
 //       f3 normal(f3 pos, float d) const    GetNormal at a march's hit, d its last distance (the centre sample),
 //       float shadow(f3 ro, f3 rd) const    softshadow,
+//       bool shadow_ok(f3 ro, f3 rd) const  what the scene adds to trace_fast_ok for a RM_TRACE_SHADOW lane,
 //       f3 render(f3 ro, f3 rd) const       a primary ray's colour,
 //       float dist(f3 p, int& k) const, void attrs(int k, f3 p, int&, float&, f3&) const
 //                                           as Scene's below, for the points of sdf_fast_ok (rm_sdf.hpp),
@@ -296,7 +297,8 @@ __device__ __forceinline__ void trace_body(const Frame& F, const TraceArgs& A, c
   if (i >= A.n) return;
   const f3 ro = trace_load3(A.origins, i), rd = trace_load3(A.dirs, i);
   const uint32_t flags = A.flags;
-  const bool ok = trace_fast_ok(ro, rd);
+  // (shadow_ok: the scene's own term for a shadow query, whose march has no escape test)
+  const bool ok = trace_fast_ok(ro, rd) && (!(flags & RM_TRACE_SHADOW) || fast.shadow_ok(ro, rd));
   TraceRec r = trace_miss();
   if (ok) {
     if (flags & RM_TRACE_SHADOW) {

@@ -79,6 +79,16 @@ def _bind(L: C.CDLL) -> C.CDLL:
     L.rmo_quantize.restype = C.c_uint8
     L.rmo_quantize.argtypes = [C.c_float]
     L.rmo_max_threads.restype = C.c_int
+    _PP = C.POINTER(rm_primitive)
+    L.rmo_trace_rays.restype = C.c_int
+    L.rmo_trace_rays.argtypes = [_PU, _PP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_uint32, C.c_void_p]
+    L.rmo_march_steps.restype = C.c_int
+    L.rmo_march_steps.argtypes = [_PU, _PP, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int32, C.c_void_p]
+    L.rmo_sdf_points.restype = C.c_int
+    L.rmo_sdf_points.argtypes = [_PU, _PP, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -166,6 +176,64 @@ def render_ray(u: rm_uniforms, ro, rd) -> np.ndarray:
     out = _F3()
     lib().rmo_render_ray(C.byref(u), _F3(*ro), _F3(*rd), out)
     return np.array(out, np.float32)
+
+
+def _table(scene):
+    if not scene:
+        return None, 0
+    return (rm_primitive * len(scene))(*scene), len(scene)
+
+
+def _rays(o, d):
+    o, d = np.ascontiguousarray(o, np.float32), np.ascontiguousarray(d, np.float32)
+    if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+        raise ValueError("rays: origins and dirs must both be (n, 3)")
+    return o, d
+
+
+def trace_rays(u: rm_uniforms, o, d, flags: int = 0,
+               scene: Optional[Sequence[rm_primitive]] = None) -> np.ndarray:
+    """rm_trace_rays as the oracle answers it (rmo_trace_rays): one rmarch.RAY_HIT_DTYPE
+    record per ray (o[i], d[i]); ``scene``: a runtime table (None: the GLSL's own scene)."""
+    from rmarch import RAY_HIT_DTYPE
+    o, d = _rays(o, d)
+    hits = np.zeros(len(o), RAY_HIT_DTYPE)
+    tbl, n = _table(scene)
+    if lib().rmo_trace_rays(C.byref(u), tbl, n, o.ctypes.data, d.ctypes.data, len(o), int(flags),
+                            hits.ctypes.data) != 0:
+        raise ValueError("rmo_trace_rays: bad arguments")
+    return hits
+
+
+def march_steps(u: rm_uniforms, o, d, reflected: bool = False,
+                scene: Optional[Sequence[rm_primitive]] = None) -> np.ndarray:
+    """The sdf() calls of each ray's march (rmo_march_steps): 512 / 256 is the step cap."""
+    o, d = _rays(o, d)
+    steps = np.zeros(len(o), np.uint32)
+    tbl, n = _table(scene)
+    if lib().rmo_march_steps(C.byref(u), tbl, n, o.ctypes.data, d.ctypes.data, len(o),
+                             int(reflected), steps.ctypes.data) != 0:
+        raise ValueError("rmo_march_steps: bad arguments")
+    return steps
+
+
+def sdf_points(u: rm_uniforms, p, scene: Optional[Sequence[rm_primitive]] = None,
+               normal: bool = False) -> dict:
+    """sdf() at points (rmo_sdf_points): {"dist", "id", "winner"} and, with ``normal``,
+    "normal" (GetNormal); winner is the opU winner's entry index."""
+    p = np.ascontiguousarray(p, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("sdf_points: points must be (n, 3)")
+    out = {"dist": np.zeros(len(p), np.float32), "id": np.zeros(len(p), np.int32),
+           "winner": np.zeros(len(p), np.int32)}
+    if normal:
+        out["normal"] = np.zeros((len(p), 3), np.float32)
+    tbl, n = _table(scene)
+    if lib().rmo_sdf_points(C.byref(u), tbl, n, p.ctypes.data, len(p), out["dist"].ctypes.data,
+                            out["id"].ctypes.data, out["winner"].ctypes.data,
+                            out["normal"].ctypes.data if normal else None) != 0:
+        raise ValueError("rmo_sdf_points: bad arguments")
+    return out
 
 
 def pixel(u: rm_uniforms, W: int, H: int, px: int, py: int) -> np.ndarray:

@@ -599,3 +599,130 @@ void rmo_pixel(const rm_uniforms *u, int32_t W, int32_t Hh, int32_t px, int32_t 
   memset(&c, 0, sizeof c);
   pixel(R, W, Hh, px, py, out, &c);
 }
+
+/* ---- batch entry points that take a runtime table --------------------------------
+ * Plain wrappers over march / get_normal / softshadow / render / sdf above: the
+ * per-ray and per-point forms of rmo_render_scene.  prims == NULL or nprims == 0
+ * is the GLSL's own scene. */
+static int rctx_table(rctx *R, const rm_uniforms *u, const rm_primitive *prims, int32_t nprims) {
+  if (!u || nprims < 0 || nprims > RM_MAX_PRIMITIVES) return -1;
+  rctx_init(R, u);
+  if (prims && nprims > 0) {
+    R->prims = prims;
+    R->nprims = nprims;
+  }
+  return 0;
+}
+
+static int trace_flags_ok(uint32_t flags) {
+  if (flags & ~(uint32_t)(RM_TRACE_REFLECTED | RM_TRACE_NORMAL | RM_TRACE_SHADE | RM_TRACE_SHADOW))
+    return 0;
+  if ((flags & RM_TRACE_SHADOW) && flags != RM_TRACE_SHADOW) return 0;
+  if ((flags & RM_TRACE_SHADE) && (flags & RM_TRACE_REFLECTED)) return 0;
+  return 1;
+}
+
+static void f3_out(float *o, v3 a) {
+  o[0] = a.x;
+  o[1] = a.y;
+  o[2] = a.z;
+}
+
+int rmo_trace_rays(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                   const float *origins, const float *dirs, int64_t n, uint32_t flags,
+                   rm_ray_hit *hits) {
+  rctx Rc;
+  if (rctx_table(&Rc, u, prims, nprims) || n < 0 || !trace_flags_ok(flags)) return -1;
+  if (n == 0) return 0;
+  if (!origins || !dirs || !hits) return -1;
+  const rctx *R = &Rc;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 16)
+#endif
+  for (int64_t i = 0; i < n; i++) {
+    v3 ro = L3(origins + 3 * i), rd = L3(dirs + 3 * i);
+    cnt c;
+    memset(&c, 0, sizeof c);
+    rm_ray_hit r;
+    memset(&r, 0, sizeof r);
+    if (flags & RM_TRACE_SHADOW) {
+      r.t = softshadow(R, ro, rd, R->k, &c); /* id, material 0 */
+    } else {
+      hit h = march(R, ro, rd, (flags & RM_TRACE_REFLECTED) != 0, &c);
+      r.t = h.hitpoint; /* a miss: the dummy {-1, 0, -1, 1.0} */
+      r.id = h.id;
+      r.material = h.material;
+      f3_out(r.albedo, h.color);
+      if ((flags & RM_TRACE_NORMAL) && h.hitpoint != -1.0f)
+        f3_out(r.normal, get_normal(R, add(ro, muls(rd, h.hitpoint)), &c));
+      if (flags & RM_TRACE_SHADE) f3_out(r.color, render(R, ro, rd, &c));
+    }
+    hits[i] = r;
+  }
+  return 0;
+}
+
+int rmo_march_steps(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                    const float *origins, const float *dirs, int64_t n, int32_t reflected,
+                    uint32_t *steps) {
+  rctx Rc;
+  if (rctx_table(&Rc, u, prims, nprims) || n < 0) return -1;
+  if (n == 0) return 0;
+  if (!origins || !dirs || !steps) return -1;
+  const rctx *R = &Rc;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 16)
+#endif
+  for (int64_t i = 0; i < n; i++) {
+    cnt c;
+    memset(&c, 0, sizeof c);
+    march(R, L3(origins + 3 * i), L3(dirs + 3 * i), reflected, &c);
+    steps[i] = (uint32_t)(reflected ? c.all.reflect : c.all.march);
+  }
+  return 0;
+}
+
+/* The entry whose RayHit sdf(pos) returns: the opU chain of sdf_table with its index
+ * kept (the GLSL's own scene in rm_default_scene's order: the ids 0, 1, 4, 5, 6, 7). */
+static int sdf_winner(const rctx *R, v3 pos) {
+  if (!R->nprims) {
+    int id = sdf(R, pos).id;
+    return id < 2 ? id : id - 2;
+  }
+  int w = 0;
+  float d = table_entry(R, &R->prims[0], pos).hitpoint;
+  for (int k = 1; k < R->nprims; k++) {
+    float e = table_entry(R, &R->prims[k], pos).hitpoint;
+    if (!(d < e)) { /* opU: (d1 < d2) ? d1 : d2 */
+      d = e;
+      w = k;
+    }
+  }
+  return w;
+}
+
+int rmo_sdf_points(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                   const float *points, int64_t n, float *dist, int32_t *id, int32_t *winner,
+                   float *normal) {
+  rctx Rc;
+  if (rctx_table(&Rc, u, prims, nprims) || n < 0) return -1;
+  if (n == 0) return 0;
+  if (!points) return -1;
+  const rctx *R = &Rc;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (int64_t i = 0; i < n; i++) {
+    v3 p = L3(points + 3 * i);
+    hit h = sdf(R, p);
+    if (dist) dist[i] = h.hitpoint;
+    if (id) id[i] = h.id;
+    if (winner) winner[i] = sdf_winner(R, p);
+    if (normal) {
+      cnt c;
+      memset(&c, 0, sizeof c);
+      f3_out(normal + 3 * i, get_normal(R, p, &c));
+    }
+  }
+  return 0;
+}

@@ -77,6 +77,34 @@ void rmo_pixel(const rm_uniforms *u, int32_t W, int32_t H, int32_t px, int32_t p
 uint8_t rmo_quantize(float c);
 int rmo_max_threads(void);
 
+/* Batch forms over a runtime scene table: what rmo_render_scene is to rmo_render,
+ * for caller-supplied rays and points.  prims == NULL or nprims == 0 is the GLSL's
+ * own scene; rays and points are independent (an OpenMP loop).  Each returns 0,
+ * or -1 on bad arguments (n == 0 writes nothing and returns 0).
+ *
+ * rmo_trace_rays fills hits[i] for ray (origins[i], dirs[i]), [n][3] floats each,
+ * with the meaning include/rm_api.h gives the RM_TRACE_* flags: RayMarch (or
+ * reflectedRay under REFLECTED) gives t, id, material, albedo, a miss the dummy
+ * {-1, -1, 1.0, zeros}; normal = GetNormal(ro + rd * t) under NORMAL on a hit,
+ * else 0; color = render(ro, rd) under SHADE, else 0; SHADOW alone puts
+ * softshadow(ro, rd, k) in t, k from u->shadow_mode, and zeros elsewhere.
+ * ro + rd * t is one float32 multiply and one add per component, as in render().
+ * Unknown flag bits, SHADOW with another flag and SHADE | REFLECTED return -1. */
+int rmo_trace_rays(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                   const float *origins, const float *dirs, int64_t n, uint32_t flags,
+                   rm_ray_hit *hits);
+/* steps[i]: the sdf() calls of ray i's RayMarch (reflectedRay if reflected);
+ * 512 (256) is a ray that ended at the step cap. */
+int rmo_march_steps(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                    const float *origins, const float *dirs, int64_t n, int32_t reflected,
+                    uint32_t *steps);
+/* sdf(points[i]) and GetNormal(points[i]); every output may be NULL.  dist [n],
+ * id [n] (RayHit.id), winner [n] (the opU winner's entry index; for the GLSL's own
+ * scene its index in rm_default_scene's order), normal [n][3]. */
+int rmo_sdf_points(const rm_uniforms *u, const rm_primitive *prims, int32_t nprims,
+                   const float *points, int64_t n, float *dist, int32_t *id, int32_t *winner,
+                   float *normal);
+
 #ifdef __cplusplus
 }
 #endif

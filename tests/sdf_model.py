@@ -1,12 +1,15 @@
 """The expected values of SDF field queries on runtime scene tables (a helper, not a test).
 
-The oracle exports rmo_sdf / rmo_get_normal for the built-in scene only; its
-table sdf is static.  This module restates table_entry, sdf_table and get_normal
-of oracle/rm_oracle.c in vectorised numpy float32: one numpy operation per C
-operation, in the same order (numpy's float32 + - * / sqrt are the IEEE
-operations and are never contracted).  blend is libm's sinf through ctypes,
-gmin / gmax are the GLSL selects, normalize is v * (1 / sqrt(dot)).
-tests/test_sdf_model.py pins it to the oracle bit for bit on the default table.
+This module restates table_entry, sdf_table and get_normal of oracle/rm_oracle.c
+in vectorised numpy float32: one numpy operation per C operation, in the same
+order (numpy's float32 + - * / sqrt are the IEEE operations and are never
+contracted).  blend is libm's sinf through ctypes, gmin / gmax are the GLSL
+selects, normalize is v * (1 / sqrt(dot)).  It was written when the oracle
+exported rmo_sdf / rmo_get_normal for the built-in scene only.
+tests/test_sdf_model.py pins it to those bit for bit on the default table, and
+tests/test_oracle_trace.py to the oracle's own table sdf (rmo_sdf_points:
+distance, id, winner and normal) on the random, floor-last and 30-entry tables
+tests/test_gpu_sdf.py uses.
 """
 import ctypes as C
 import ctypes.util
