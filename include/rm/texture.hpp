@@ -75,6 +75,14 @@ inline int dispatchAdaptiveEdges(rm_ctx* p, const rm_aa_criteria* criteria = nul
   if (!criteria) rm_aa_criteria_init(&c);
   return rm_dispatch_adaptive_edges(p, criteria ? criteria : &c);
 }
+// the frame supersampled at a sample pattern's offsets (rm_dispatch_pattern): a preset
+// RM_PATTERN_* (the default, GRID2: four re-centred samples), or the caller's own pattern
+inline int dispatchPattern(rm_ctx* p, int preset = RM_PATTERN_GRID2) {
+  rm_sample_pattern s;
+  const int rc = rm_sample_pattern_init(&s, preset);
+  return rc != RM_OK ? rc : rm_dispatch_pattern(p, &s);
+}
+inline int dispatchPattern(rm_ctx* p, const rm_sample_pattern& pattern) { return rm_dispatch_pattern(p, &pattern); }
 inline int memoryBarrier(rm_ctx* p) { return rm_synchronize(p); }
 
 }  // namespace rm

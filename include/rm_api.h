@@ -779,6 +779,77 @@ int rm_aa_criteria_init(rm_aa_criteria *c);
  * field outside the ranges above.  Asynchronous. */
 int rm_dispatch_adaptive_edges(rm_ctx *ctx, const rm_aa_criteria *criteria);
 
+/* ---- sample patterns: a frame supersampled at caller-chosen offsets --------------
+ * An extension.  rm_dispatch_pattern renders the whole frame with n sample rays
+ * per pixel at the offsets of an rm_sample_pattern, in pixels from the AA-off
+ * frame's ray (the ray rm_pick casts), and stores their mean: a re-centred or
+ * rotated grid that registers with the AA-off frame and the G-buffer, 8, 9 or 16
+ * samples per pixel, or one jittered sample per frame (n = 1) for a caller's own
+ * temporal accumulation.
+ *
+ * The rule.  Every operation is one IEEE single-precision operation in the order
+ * written, with no FMA.
+ *
+ *  - uv.  x0 = (float)(2 px - W) / (float)W and y0 = (float)(2 py - H) / (float)H
+ *    (glsl:301-305).  ox_s = (2.0f * dx[s]) / (float)W and
+ *    oy_s = (2.0f * dy[s]) / (float)H.  Without the flag: ux_s = x0 + ox_s.  With
+ *    RM_PATTERN_CUMULATIVE: ux_0 = x0 + ox_0 and ux_s = ux_(s-1) + ox_s.  y is
+ *    formed the same way.
+ *  - Sample.  c_s = render(castRay(ux_s, uy_s)).  This is what a SHADE trace of
+ *    that ray returns (rm_trace_rays with RM_TRACE_SHADE).
+ *  - Pixel.  sum = c_0; sum = sum + c_s for s = 1..n-1 in order;
+ *    out = sum / (float)n; alpha 1.0f.  RGBA8 is the usual quantisation of out
+ *    (round(clamp(c, 0, 1) * 255), NaN -> 0).
+ *  - Two anchors follow from the rule.  RM_PATTERN_REFERENCE gives the AA-on
+ *    rm_dispatch frame bit for bit: 2 * 0.125f is exactly the shader's 0.25.
+ *    n = 1, dx = dy = 0 gives the AA-off frame.
+ *
+ *  - Validation: struct_size is sizeof(rm_sample_pattern), flags has no unknown
+ *    bit, n is in 1..RM_MAX_SAMPLES, and every read offset (index < n) is finite
+ *    with |d| <= 16; otherwise RM_ERR_INVALID, with the reason in rm_last_error
+ *    for rm_dispatch_pattern.  Entries past n are not read.
+ *  - u.AA is ignored and the context's uniforms stay as they are; bounceVar,
+ *    shadow_mode, iTime, the light and the camera apply as in rm_dispatch.
+ *  - Afterwards the context reads as after an rm_dispatch (rm_read_rgba8 /
+ *    _rgba32f, rm_get_output_rgba8, rm_set_output_rgba8, rm_wait_output,
+ *    rm_set_stream, rm_synchronize).  Nothing is sticky: the next rm_dispatch is
+ *    what it always was.  With rm_enable_timing the call is one bracketed launch.
+ *    The pattern's uv table is uploaded when the pattern differs from the last
+ *    call's; a repeated pattern uploads nothing.
+ *  - This version: one-device, whole-frame contexts; the built-in scene and
+ *    rm_set_scene tables (with rm_scene_specialize on the generic table code
+ *    renders, as the adaptive refinement does: same values).  RM_ERR_STATE on a
+ *    context with counters, nshards > 1, a communicator, ngpus >= 1,
+ *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay, no
+ *    pattern refinement in the adaptive calls, no accumulation across calls. */
+#define RM_HAS_SAMPLE_PATTERN 1
+#define RM_MAX_SAMPLES 16
+#define RM_PATTERN_CUMULATIVE 1u      /* flags: offsets are increments, the GLSL's x += o / W */
+typedef struct rm_sample_pattern {    /* 140 bytes */
+  uint32_t struct_size;               /* sizeof(rm_sample_pattern), else RM_ERR_INVALID */
+  uint32_t flags;                     /* 0 or RM_PATTERN_CUMULATIVE; unknown bits: RM_ERR_INVALID */
+  int32_t  n;                         /* 1..RM_MAX_SAMPLES */
+  float    dx[RM_MAX_SAMPLES];        /* pixels, from the AA-off frame's ray (rm_pick's) */
+  float    dy[RM_MAX_SAMPLES];
+} rm_sample_pattern;
+/* presets: every offset is a dyadic rational, so 2 d is exact */
+#define RM_PATTERN_REFERENCE 0  /* n 4, CUMULATIVE, dx {.125,.375,.125,.375}, dy {.125,.125,.375,.375} */
+#define RM_PATTERN_GRID2     1  /* n 4,  {-.25,+.25}^2, x fastest */
+#define RM_PATTERN_RGSS      2  /* n 4,  (.125,.375) (-.375,.125) (.375,-.125) (-.125,-.375) */
+#define RM_PATTERN_GRID3     3  /* n 9,  {-.34375, 0, +.34375}^2 (11/32: the multiple of 1/32 nearest 1/3), x fastest */
+#define RM_PATTERN_GRID4     4  /* n 16, {-.375,-.125,+.125,+.375}^2, x fastest */
+/* struct_size, flags, n and the offsets of a preset, the entries past n zero.
+ * RM_ERR_INVALID for NULL or an unknown preset (nothing written). */
+int rm_sample_pattern_init(rm_sample_pattern *p, int32_t preset);
+/* The uv of every pixel column and row by the rule above: uvx [width][n], uvy
+ * [height][n], either possibly NULL.  Pure: no context, no device.
+ * RM_ERR_INVALID for an invalid pattern or a width / height outside 1..65536. */
+int rm_pattern_uv_table(const rm_sample_pattern *p, int32_t width, int32_t height,
+                        float *uvx, float *uvy);
+/* The frame of the pattern.  RM_ERR_INVALID for a null context or pattern
+ * (nothing written) or an invalid pattern.  Asynchronous. */
+int rm_dispatch_pattern(rm_ctx *ctx, const rm_sample_pattern *p);
+
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process
  * per GPU (torch.distributed.run, MPI).  Rank 0 creates an id and broadcasts it

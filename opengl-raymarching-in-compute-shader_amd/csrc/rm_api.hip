@@ -163,9 +163,10 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
 // scene's, or for a table always the generic code (its specialised kernels render
 // frames only).
 const SceneKernels& rm::scene_kernels(const rm_ctx* c) {
-  static const SceneKernels builtin{launch_trace, launch_sdf_points, launch_sdf_grid, launch_adapt_refine};
+  static const SceneKernels builtin{launch_trace, launch_sdf_points, launch_sdf_grid, launch_adapt_refine,
+                                    launch_pattern};
   static const SceneKernels table{launch_table_trace, launch_table_sdf_points, launch_table_sdf_grid,
-                                  launch_table_adapt_refine};
+                                  launch_table_adapt_refine, launch_table_pattern};
   return c->nprims ? table : builtin;
 }
 
@@ -201,11 +202,21 @@ void free_all(rm_ctx* c) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  for (DevBuf* b : {&c->stage_in, &c->stage_out, &c->mesh_vol, &c->mesh_waves, &c->mesh_idx, &c->mesh_attr}) {
+  for (DevBuf* b : {&c->stage_in, &c->stage_out, &c->mesh_vol, &c->mesh_waves, &c->mesh_idx, &c->mesh_attr,
+                    &c->pat_uv}) {
     if (b->p) (void)hipFree(b->p);
     *b = DevBuf();
   }
   c->aa_dispatched = false;
+  c->pat.n = 0;
+  if (c->pat_ev) {
+    if (c->pat_ev_pending) (void)hipEventSynchronize(c->pat_ev);
+    (void)hipEventDestroy(c->pat_ev);
+  }
+  c->pat_ev = nullptr;
+  c->pat_ev_pending = false;
+  if (c->pat_host) (void)hipHostFree(c->pat_host);
+  c->pat_host = nullptr;
   if (c->gstream) (void)hipStreamSynchronize(c->gstream);
   for (uint8_t* p : c->ring8) (void)hipFree(p);
   for (float* p : c->ring32) (void)hipFree(p);

@@ -31,17 +31,10 @@
 
 using namespace rm;
 
-namespace {
-
-size_t adapt_tiles(const rm_ctx* c) {
-  const size_t t = rmd::kAdaptTile;
-  return ((c->cfg.width + t - 1) / t) * ((c->cfg.height + t - 1) / t);
-}
-
 // RM_ERR_STATE for the contexts this version does not serve, naming the call.
 // gbuf_ok: the call admits a G-buffer context (rm_dispatch_adaptive_edges, and
-// the mask's pointer for it).
-int refuse(rm_ctx* c, const char* call, bool gbuf_ok = false) {
+// the mask's pointer for it).  rm_dispatch_pattern (rm_api_pattern.hip) refuses the same contexts.
+int rm::refuse_extension(rm_ctx* c, const char* call, bool gbuf_ok) {
   const std::string who = std::string(call) + ": ";
   if (!c->subs.empty() || c->cfg.ngpus >= 1)
     return fail(c, RM_ERR_STATE, who + "not available on a multi-GPU context (rm_config.ngpus)");
@@ -52,6 +45,13 @@ int refuse(rm_ctx* c, const char* call, bool gbuf_ok = false) {
   if (has_gbuf(c) && !gbuf_ok) return fail(c, RM_ERR_STATE, who + "not available on a G-buffer context (RM_OUT_GBUFFER)");
   if (c->graph_on) return fail(c, RM_ERR_STATE, who + "not available with rm_graph_enable on");
   return RM_OK;
+}
+
+namespace {
+
+size_t adapt_tiles(const rm_ctx* c) {
+  const size_t t = rmd::kAdaptTile;
+  return ((c->cfg.width + t - 1) / t) * ((c->cfg.height + t - 1) / t);
 }
 
 // The context's buffers, on first use; kept until rm_destroy.
@@ -148,7 +148,7 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
 
 // What every such dispatch checks and prepares before its frame.
 int begin(rm_ctx* c, const char* call, bool gbuf_ok = false) {
-  int rc = refuse(c, call, gbuf_ok);
+  int rc = refuse_extension(c, call, gbuf_ok);
   if (rc != RM_OK) return rc;
   if ((rc = check_uniforms(c, c->u)) != RM_OK) return rc;
   if ((rc = set_device(c)) != RM_OK) return rc;
@@ -242,7 +242,7 @@ int rm_read_aa_mask(rm_ctx* c, uint8_t* dst, size_t row_pitch, int flip_y) {
 
 int rm_get_aa_mask(rm_ctx* c, void** device_ptr) {
   if (!c || !device_ptr) return RM_ERR_INVALID;
-  int rc = refuse(c, "rm_get_aa_mask", true);
+  int rc = refuse_extension(c, "rm_get_aa_mask", true);
   if (rc != RM_OK) return rc;
   if ((rc = set_device(c)) != RM_OK) return rc;
   if ((rc = ensure_buffers(c)) != RM_OK) return rc;

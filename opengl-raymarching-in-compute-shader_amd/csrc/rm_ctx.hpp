@@ -3,7 +3,7 @@
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
 // rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
 // rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling),
-// rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
+// rm_api_pattern.hip (sample-pattern frames), rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
 // families share: their frame constants, checks and staging buffers).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
@@ -19,6 +19,7 @@
 #include "rm_internal.hpp"
 #include "rm_jit.hpp"
 #include "rm_mesh_args.hpp"
+#include "rm_pattern_args.hpp"
 #include "rm_scene.hpp"
 #include "rm_sdf_args.hpp"
 
@@ -69,6 +70,10 @@ hipError_t launch_adapt_edges(const rmd::AdaptArgs& A, const rmd::EdgeArgs& E, b
 hipError_t launch_adapt_list(const rmd::AdaptArgs& A, hipStream_t s);
 hipError_t launch_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
 hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& A, int waves, hipStream_t s);
+// a sample-pattern frame (rm_pattern.hip, rm_table_pattern.hip): frame F, whose grid_x / grid_y
+// are pixel_grid's with aa set, at the pattern's device table P
+hipError_t launch_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
+hipError_t launch_table_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
 // SDF mesh extraction (rm_mesh.hip), every dim >= 2: the waves' ballots and counts of M.vol,
 // their scans and the mesh's counts; then the vertices below M.vcap and the quads below
 // M.qcap; the device call's records below min(counts[0], vcap) out of n >= 1 staged ones
@@ -107,6 +112,7 @@ struct SceneKernels {
   decltype(launch_sdf_points)* sdf_points;
   decltype(launch_sdf_grid)* sdf_grid;
   decltype(launch_adapt_refine)* adapt_refine;
+  decltype(launch_pattern)* pattern;
 };
 
 // A device buffer the context owns and grows on demand (rm_api_query.hip ensure).
@@ -223,6 +229,14 @@ struct rm_ctx {
   // arrays (rm_mesh_args.hpp); rm_sdf_mesh's staging of the indices; rm_sdf_mesh_device's of
   // the records
   rm::DevBuf mesh_vol, mesh_waves, mesh_idx, mesh_attr;
+  // sample-pattern frames (rm_api_pattern.hip): the last pattern, its uv table on the device
+  // (uvx [width][n], then uvy [height][n]) and the range of its values per axis
+  rm::DevBuf pat_uv;
+  rm_sample_pattern pat{};  // pat.n == 0: none yet
+  float pat_lo[2] = {0, 0}, pat_hi[2] = {0, 0};
+  float* pat_host = nullptr;     // the table's pinned host copy, the source of the upload
+  hipEvent_t pat_ev = nullptr;   // the last upload, on the stream it was queued on
+  bool pat_ev_pending = false;   // recorded and not yet waited for: pat_host is still being read
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;
@@ -351,6 +365,12 @@ rmd::SdfGridArgs sdf_grid_args(const rm_sdf_grid_desc* g, void* dist, void* ids)
 // b of at least `need` bytes, replaced when too small (hipFree waits for the device, so
 // nothing pending uses the old one); `what` names it in RM_ERR_NOMEM.
 int ensure(rm_ctx* c, DevBuf& b, size_t need, const char* what);
+
+// ---- rm_api_adaptive.hip -----------------------------------------------------------------
+// RM_ERR_STATE, naming `call`, for the contexts the adaptive dispatches and rm_dispatch_pattern
+// do not serve: multi-device, communicator, sharded, counting, graph-replay and (unless
+// gbuf_ok) G-buffer contexts.
+int refuse_extension(rm_ctx* c, const char* call, bool gbuf_ok = false);
 
 // ---- rm_api_graph.hip: hipGraph replay -----------------------------------------------------
 void graph_release(rm_ctx* c);

@@ -234,4 +234,99 @@ UvTable uv_table(int W, int H) {
   return t;
 }
 
+const char* pattern_invalid(const rm_sample_pattern* p) {
+  if (p->struct_size != sizeof(rm_sample_pattern)) return "rm_sample_pattern.struct_size is not sizeof(rm_sample_pattern)";
+  if (p->flags & ~RM_PATTERN_CUMULATIVE) return "rm_sample_pattern.flags has an unknown bit";
+  if (p->n < 1 || p->n > RM_MAX_SAMPLES) return "rm_sample_pattern.n must be in 1..RM_MAX_SAMPLES";
+  for (int s = 0; s < p->n; ++s)
+    // (written so that a NaN fails)
+    if (!(std::fabs(p->dx[s]) <= 16.0f) || !(std::fabs(p->dy[s]) <= 16.0f))
+      return "every offset below n must be finite and within 16 pixels";
+  return nullptr;
+}
+
+void pattern_uv(const rm_sample_pattern& p, int W, int H, float* uvx, float* uvy, float lo[2], float hi[2]) {
+  const int n = p.n;
+  const bool cumulative = (p.flags & RM_PATTERN_CUMULATIVE) != 0;
+  for (int a = 0; a < 2; ++a) {
+    const int dim = a ? H : W;
+    const float* d = a ? p.dy : p.dx;
+    float* out = a ? uvy : uvx;
+    const float dimf = (float)dim;
+    float off[RM_MAX_SAMPLES];
+    for (int s = 0; s < n; ++s) off[s] = (2.0f * d[s]) / dimf;
+    lo[a] = INFINITY;
+    hi[a] = -INFINITY;
+    for (int i = 0; i < dim; ++i) {
+      const float v0 = (float)(2 * i - dim) / dimf;
+      float v = v0;
+      for (int s = 0; s < n; ++s) {
+        v = (cumulative ? v : v0) + off[s];
+        if (out) out[(size_t)i * n + s] = v;
+        lo[a] = std::fmin(lo[a], v);
+        hi[a] = std::fmax(hi[a], v);
+      }
+    }
+  }
+}
+
 }  // namespace rm
+
+extern "C" {
+
+int rm_sample_pattern_init(rm_sample_pattern* p, int32_t preset) {
+  if (!p || preset < RM_PATTERN_REFERENCE || preset > RM_PATTERN_GRID4) return RM_ERR_INVALID;
+  std::memset(p, 0, sizeof *p);
+  p->struct_size = (uint32_t)sizeof *p;
+  auto grid = [&](const float* v, int m) {  // {v}^2, x fastest
+    p->n = m * m;
+    for (int j = 0; j < m; ++j)
+      for (int i = 0; i < m; ++i) {
+        p->dx[j * m + i] = v[i];
+        p->dy[j * m + i] = v[j];
+      }
+  };
+  switch (preset) {
+    case RM_PATTERN_REFERENCE: {
+      const float dx[4] = {0.125f, 0.375f, 0.125f, 0.375f}, dy[4] = {0.125f, 0.125f, 0.375f, 0.375f};
+      p->flags = RM_PATTERN_CUMULATIVE;
+      p->n = 4;
+      std::memcpy(p->dx, dx, sizeof dx);
+      std::memcpy(p->dy, dy, sizeof dy);
+      break;
+    }
+    case RM_PATTERN_GRID2: {
+      const float v[2] = {-0.25f, 0.25f};
+      grid(v, 2);
+      break;
+    }
+    case RM_PATTERN_RGSS: {
+      const float dx[4] = {0.125f, -0.375f, 0.375f, -0.125f}, dy[4] = {0.375f, 0.125f, -0.125f, -0.375f};
+      p->n = 4;
+      std::memcpy(p->dx, dx, sizeof dx);
+      std::memcpy(p->dy, dy, sizeof dy);
+      break;
+    }
+    case RM_PATTERN_GRID3: {
+      const float v[3] = {-0.34375f, 0.0f, 0.34375f};
+      grid(v, 3);
+      break;
+    }
+    default: {
+      const float v[4] = {-0.375f, -0.125f, 0.125f, 0.375f};
+      grid(v, 4);
+      break;
+    }
+  }
+  return RM_OK;
+}
+
+int rm_pattern_uv_table(const rm_sample_pattern* p, int32_t width, int32_t height, float* uvx, float* uvy) {
+  if (!p || rm::pattern_invalid(p)) return RM_ERR_INVALID;
+  if (width < 1 || width > 65536 || height < 1 || height > 65536) return RM_ERR_INVALID;
+  float lo[2], hi[2];
+  rm::pattern_uv(*p, width, height, uvx, uvy, lo, hi);
+  return RM_OK;
+}
+
+}  // extern "C"

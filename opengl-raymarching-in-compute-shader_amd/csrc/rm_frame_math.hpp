@@ -29,4 +29,14 @@ struct UvTable {
 };
 UvTable uv_table(int W, int H);
 
+// Sample patterns (include/rm_api.h RM_HAS_SAMPLE_PATTERN; rm_sample_pattern_init and
+// rm_pattern_uv_table are defined beside these, in rm_frame_math.hip).
+// Why p (not null) is no valid pattern, or null for a valid one.
+const char* pattern_invalid(const rm_sample_pattern* p);
+// The uv of a valid pattern's samples by the header's rule, for a W x H frame: uvx
+// [W][n] and uvy [H][n], either possibly null; and the range of the columns'
+// (lo / hi [0]) and the rows' ([1]) values, which is what unit_rd_check has to cover
+// for a pattern frame (the context's uv_lo / uv_hi cover the reference's offsets only).
+void pattern_uv(const rm_sample_pattern& p, int W, int H, float* uvx, float* uvy, float lo[2], float hi[2]);
+
 }  // namespace rm

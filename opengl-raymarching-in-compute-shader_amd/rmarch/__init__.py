@@ -48,6 +48,15 @@ RM_AA_EDGE_ID = 2       # p.id != q.id (a miss has id -1)
 RM_AA_EDGE_DEPTH = 4    # both hit and |p.t - q.t| > depth_rel * min(p.t, q.t)
 RM_AA_EDGE_NORMAL = 8   # both hit and dot(p.normal, q.normal) < normal_cos
 RM_AA_EDGE_ALBEDO = 16  # some albedo component differs (checker edges)
+# sample patterns (rm_dispatch_pattern): flags and presets
+RM_HAS_SAMPLE_PATTERN = 1  # Renderer.dispatch_pattern
+RM_MAX_SAMPLES = 16
+RM_PATTERN_CUMULATIVE = 1  # offsets are increments, the GLSL's x += o / W
+RM_PATTERN_REFERENCE = 0   # n 4, CUMULATIVE: the AA-on frame's samples
+RM_PATTERN_GRID2 = 1       # n 4, {-.25, +.25}^2, x fastest
+RM_PATTERN_RGSS = 2        # n 4, rotated grid
+RM_PATTERN_GRID3 = 3       # n 9, {-.34375, 0, +.34375}^2, x fastest
+RM_PATTERN_GRID4 = 4       # n 16, {-.375, -.125, +.125, +.375}^2, x fastest
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -118,6 +127,11 @@ class rm_config(C.Structure):
 class rm_aa_criteria(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("edges", C.c_uint32), ("color_threshold", C.c_int32),
                 ("depth_rel", C.c_float), ("normal_cos", C.c_float)]
+
+
+class rm_sample_pattern(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n", C.c_int32),
+                ("dx", C.c_float * RM_MAX_SAMPLES), ("dy", C.c_float * RM_MAX_SAMPLES)]
 
 
 class rm_camera_state(C.Structure):
@@ -328,6 +342,9 @@ _SIGS = {
     "rm_aa_refined": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rm_aa_criteria_init": (C.c_int, [C.POINTER(rm_aa_criteria)]),
     "rm_dispatch_adaptive_edges": (C.c_int, [_P, C.POINTER(rm_aa_criteria)]),
+    "rm_sample_pattern_init": (C.c_int, [C.POINTER(rm_sample_pattern), C.c_int32]),
+    "rm_pattern_uv_table": (C.c_int, [C.POINTER(rm_sample_pattern), C.c_int32, C.c_int32, _P, _P]),
+    "rm_dispatch_pattern": (C.c_int, [_P, C.POINTER(rm_sample_pattern)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -385,6 +402,37 @@ def sweep_uniforms(frame: int, nframes: int = 120, bounces: int = 0, aa: bool = 
     _check(lib().rm_sweep_uniforms(frame, nframes, bounces, 1 if aa else 0, shadow_mode,
                                    C.byref(u)))
     return u
+
+
+# ---- sample patterns (rm_dispatch_pattern) ---------------------------------------------
+def sample_pattern(preset: int = RM_PATTERN_REFERENCE) -> rm_sample_pattern:
+    """The preset RM_PATTERN_* (rm_sample_pattern_init)."""
+    p = rm_sample_pattern()
+    _check(lib().rm_sample_pattern_init(C.byref(p), int(preset)))
+    return p
+
+
+def custom_pattern(dx: Sequence[float], dy: Sequence[float], cumulative: bool = False) -> rm_sample_pattern:
+    """A pattern of len(dx) == len(dy) samples at (dx[s], dy[s]) pixels from the AA-off
+    frame's ray; cumulative: the offsets are increments (RM_PATTERN_CUMULATIVE)."""
+    if len(dx) != len(dy) or not 1 <= len(dx) <= RM_MAX_SAMPLES:
+        raise ValueError("custom_pattern: 1..RM_MAX_SAMPLES offsets on both axes")
+    p = rm_sample_pattern(struct_size=C.sizeof(rm_sample_pattern),
+                          flags=RM_PATTERN_CUMULATIVE if cumulative else 0, n=len(dx))
+    for s, (x, y) in enumerate(zip(dx, dy)):
+        p.dx[s], p.dy[s] = float(x), float(y)
+    return p
+
+
+def pattern_uv_table(p: rm_sample_pattern, width: int, height: int) -> tuple:
+    """The uv of every pixel column and row under pattern p (rm_pattern_uv_table): float32
+    arrays (width, n) and (height, n).  Pure host math; needs no GPU."""
+    n = int(p.n) if 1 <= int(p.n) <= RM_MAX_SAMPLES else 1
+    uvx, uvy = np.empty((width, n), np.float32), np.empty((height, n), np.float32)
+    rc = lib().rm_pattern_uv_table(C.byref(p), int(width), int(height), uvx.ctypes.data, uvy.ctypes.data)
+    if rc < 0:
+        raise RMError(rc, "rm_pattern_uv_table: invalid pattern or frame size")
+    return uvx, uvy
 
 
 # ---- Camera (source/camera.hpp:12-35) --------------------------------------------------
@@ -692,6 +740,19 @@ class Renderer:
         n = C.c_int64(0)
         _check(lib().rm_aa_refined(self._h, C.byref(n)), self._h)
         return int(n.value)
+
+    # -- sample patterns (rm_dispatch_pattern)
+    def dispatch_pattern(self, u: Optional[rm_uniforms] = None,
+                         pattern=RM_PATTERN_REFERENCE) -> None:
+        """The frame supersampled at a pattern's offsets (rm_dispatch_pattern): `pattern` is
+        an rm_sample_pattern (sample_pattern, custom_pattern) or a preset RM_PATTERN_*.  Every
+        pixel is the mean of its samples in the pattern's order; RM_PATTERN_REFERENCE is the
+        AA-on frame bit for bit, one sample at (0, 0) the AA-off frame.  u.AA is ignored.
+        Asynchronous; reads back like dispatch()."""
+        if u is not None:
+            self.set_uniforms(u)
+        p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
+        _check(lib().rm_dispatch_pattern(self._h, C.byref(p)), self._h)
 
     def read_frame_rgba8(self, k: int, flip_y: bool = False) -> np.ndarray:
         out = np.empty((self.rows, self.width, 4), np.uint8)
