@@ -88,6 +88,8 @@ rmd::Frame rm::make_frame(const rm_ctx* c) {
   // device's former per-call expression in the same float operations
   F.shc = (F.k == INFINITY) ? 0.0f : (1.0f + 0x1p-9f) / F.k * (1.0f + 0x1p-12f);
   F.persp = 45.0f * static_cast<float>(0.01745329251994329576923690768489);
+  // the shadow exit's light-in-ball test (rm_scene.hpp), once per frame
+  F.light_ball = rmd::light_in_ball(F.lpos) ? 1 : 0;
   F.uvx = c->d_uv;
   F.uvy = c->d_uv + (size_t)5 * c->cfg.width;
   F.uv_exact = c->uv_exact ? 1 : 0;
@@ -274,6 +276,19 @@ int rm_debug_stats(unsigned long long *out64) {
   return rm::debug_stats(out64, true) == hipSuccess ? 0 : -1;
 }
 #endif
+
+/* Diagnostic read for the tests (not declared in rm_api.h, like rm_debug_stats;
+ * rmarch binds it on first use, Renderer.debug_frame_flags): the wave-uniform
+ * branches a frame of the context's current uniforms takes, as make_frame sets
+ * them: out2[0] = Frame::unit_rd (cast_ray's lean form, the unit march),
+ * out2[1] = Frame::light_ball (the shadow exit without the ball's bound). */
+int rm_debug_frame_flags(const rm_ctx* c, int32_t* out2) {
+  if (!c || !out2) return RM_ERR_INVALID;
+  const rmd::Frame F = rm::make_frame(c);
+  out2[0] = F.unit_rd;
+  out2[1] = F.light_ball;
+  return RM_OK;
+}
 
 const char* rm_last_error(const rm_ctx* ctx) {
   return ctx ? ctx->err.c_str() : g_create_error.c_str();

@@ -6,6 +6,7 @@
 
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #endif
 
 namespace rmd {
@@ -64,6 +65,30 @@ __device__ __forceinline__ float sqrt_cr_nonneg(float x) {
   const bool small = x < 0x1p-96f;
   const float s = sqrt_core(small ? x * 0x1p64f : x);
   return small ? s * 0x1p-32f : s;
+}
+
+// sqrt_cr_nonneg behind a wave vote: when every active lane's x is >= 2^-96 the
+// 2^64 pre-scale of sqrt_cr_nonneg selects nothing, and the wave takes sqrt_core
+// alone (the same instructions on the same value); any lane below 2^-96, or NaN
+// (it fails the compare), sends the whole wave through the guarded form.  One
+// compare and a scalar branch where the guard spent five VALU, four of them
+// whole-slot.  Bitwise equal to sqrt_cr_nonneg on every input, whichever way the
+// vote goes (tools/exhaustive_fp.hip sqrt_vote).
+__device__ __forceinline__ float sqrt_vote(float x) {
+  if (__all(x >= SQRT_CORE_MIN)) return sqrt_core(x);
+  return sqrt_cr_nonneg(x);
+}
+
+// RGBA8 quantisation round(clamp(c, 0, 1) * 255), NaN -> 0.
+// LEAN: the clamp as one v_med3_f32: of (c, 0, 1) it returns the middle value, and
+// for a NaN c either 0 or the NaN, which the conversion turns into 0.  -0 may come
+// out as -0: (-0) * 255 + 0.5 is 0.5 all the same.  Equal to the compare-and-select
+// form on all 2^32 inputs (tools/exhaustive_fp.hip quantize), in four VALU per
+// channel where that form takes seven.  (Which kernels take LEAN: rm_kernels.hip.)
+template <bool LEAN = false>
+__device__ __forceinline__ uint32_t quantize(float c) {
+  const float v = LEAN ? __builtin_amdgcn_fmed3f(c, 0.0f, 1.0f) : ((c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f);
+  return (uint32_t)(v * 255.0f + 0.5f);
 }
 
 // x / CAP_BB correctly rounded, as a multiply by the correctly-rounded

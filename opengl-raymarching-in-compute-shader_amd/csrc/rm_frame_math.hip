@@ -159,6 +159,17 @@ void table_prep_host(const uint32_t* words, int32_t n, const float cam[3], float
 // the interior critical point, in double), and requires min |v|^2 >= 2^-38 M^2
 // (the float error of v, <= 3 sqrt(3) u M with M >= |v| the triangle bound,
 // then moves |v| by < 16 %), min |v|^2 >= 2^-80 and M^2 <= 2^100.
+//
+// What relies on a passing check besides the unit march (rm_kernels.hip march<UNIT>):
+// cast_ray's lean form (rm_scene.hpp cast_ray<LEAN>) drops the w lane of v on these
+// frames, which uses two of the conditions below: the three w components are exactly
+// 0, and X, Y, C and the uv range are finite (so v.w = (uvx 0 + uvy 0) + 0 persp is
+// +-0 and not NaN, and v.z^2 + v.w^2 is v.z^2 bit for bit).  Its root takes sqrt_vote
+// on every frame and depends on nothing here for its value; min |v|^2 >= 2^-80 with
+// the float sum within 16 % only says that the vote passes (|v|^2 > 2^-96) on these
+// frames, i.e. that they take sqrt_core alone.  Relaxing the w or the finiteness
+// condition breaks cast_ray<true>; relaxing the 2^-80 floor only sends waves through
+// the guarded root.
 bool unit_rd_check(const rm_camera& k, float persp, const float uv_lo[2], const float uv_hi[2]) {
   if (k.xAxis[3] != 0.0f || k.yAxis[3] != 0.0f || k.dir[3] != 0.0f) return false;
   double X[3], Y[3], C[3];

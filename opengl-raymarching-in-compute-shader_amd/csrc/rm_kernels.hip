@@ -31,6 +31,21 @@ constexpr int kCapI0 = 16, kCapI1 = 64;
 __device__ unsigned long long* g_wave_times;
 #endif
 
+// The once-per-wave and once-per-hit forms of DESIGN.md §4.4 item 23 (the LEAN forms
+// of cast_ray, point_light, light_in_ball and quantize, and normalize_vote) are taken
+// where the build says so, -DRM_LEAN_FIXED_WORK=1: the supersampled frame kernels'
+// object (Makefile, rm_kernels_aa.o), where they were measured to pay.  In k_pixel
+// the same changes measured 1.5 to 4 % slower per cfg2 frame, by register allocation
+// and scheduling rather than by instruction count (LOG.md "fixed work").  The counting
+// kernels keep the plain forms (with the lean ones k_sample<true> spills two VGPRs);
+// every test that compares the production image with the counting build's bit for bit
+// compares the two forms.
+#ifndef RM_LEAN_FIXED_WORK
+#define RM_LEAN_FIXED_WORK 0
+#endif
+template <bool COUNT>
+constexpr bool kLean = RM_LEAN_FIXED_WORK != 0 && !COUNT;
+
 struct Cnt {
   uint32_t rays, march, reflect, shadow, normals, lights;
 };
@@ -123,6 +138,25 @@ __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3
     t = d0;
     i0 = 2;
   }
+#ifdef RM_DBL_CAST
+  // the primary march's per-ray set-up a second time (sample_body doubles the ray)
+  if (!COUNT && !reflected) {
+    const f3 rd2 = opaque(rd);
+    LazyCull l2;
+    if (UNIT) lazy_init_unit(l2, rd2, opaque(s0), ray_s1(opaque(rdl)));
+    else lazy_init(l2, rd2, ray_rdl(rd2), opaque(s0), ray_s1(ray_rdl(rd2)));
+    if (prep) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+        lc.te[k] = vmin(lc.te[k], vmax3(F.prepv[PREP_G + k] * l2.inv2v, F.prepv[PREP_H + k] * l2.invp, 0.0f));
+      lc.tegrp = vmin(lc.tegrp, vmin(vmin3(lc.te[0], lc.te[1], lc.te[2]), lc.te[4]));
+      lc.temin = vmin(lc.temin, vmin(lc.tegrp, lc.te[3]));
+    }
+    lc.invp = vmin(lc.invp, l2.invp);
+    lc.inv2v = vmin(lc.inv2v, l2.inv2v);
+    lc.s1 = vmin(lc.s1, l2.s1);
+  }
+#endif
 #ifndef RM_STATS
   if (!COUNT) {
     // Production loop.  A lane leaves on hit | escape | proven miss; the 512 /
@@ -235,12 +269,21 @@ __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3
   const float mx = miss_T();
 #ifdef RM_STATS
   int nst = 0;  // this lane's steps (diagnostic builds)
+  const bool dn_lane = rd.y <= 0.0f && ro.y + 5.5f <= tmax;
+  bool mixed0 = false, seg_dn = false;
 #endif
   for (int i = i0;; ++i) {
 #ifdef RM_STATS
     ++nst;
     {
       const unsigned long long m = __ballot(1);
+      // wave steps the production kernel takes in a general loop although every lane
+      // left at the segment's start was a downward one: [35] / [36] primary, [55] /
+      // [56] reflected, in the segments after step kCapI0 / after kCapI1
+      if (i == i0) mixed0 = !__all(dn_lane);
+      if (i == kCapI0 + 1 || i == kCapI1 + 1) seg_dn = mixed0 && __all(dn_lane);
+      if (seg_dn && __lane_id() == __builtin_ffsll(m) - 1)
+        atomicAdd(&g_stats[(reflected ? 55 : 35) + (i > kCapI1 ? 1 : 0)], 1ull);
       if (__lane_id() == __builtin_ffsll(m) - 1) {
         atomicAdd(&g_stats[reflected ? 6 : 15], 1ull);
         atomicAdd(&g_stats[7], (unsigned long long)__popcll(m));
@@ -315,6 +358,7 @@ __device__ f3 get_normal(const Frame& F, f3 pos, Cnt& c, float c0 = 0.0f, bool c
   if (CLAIM && !COUNT && __all(claim)) {
     RM_STAT(21);
     normal_samples_plane(pos, vx, vy, vz);
+    if (kLean<COUNT>) return normalize_vote(subs(mk(vx, vy, vz), c0));
     return normalize(subs(mk(vx, vy, vz), c0));
   }
   normal_samples<HAVE_C0>(pos, F.blend, F.omblend, c0, vx, vy, vz);
@@ -358,7 +402,7 @@ __device__ __forceinline__ float softshadow_impl(const Frame& F, f3 ro, f3 rd, f
   float res = 1.0f, t = 0.0f;
   int dummy;
   RM_STAT(29);
-  const float ex = shadow_exit_init(F.shc, ro, rd, rdl, light_in_ball(F));
+  const float ex = shadow_exit_init(F.shc, ro, rd, rdl, light_in_ball<kLean<COUNT>>(F));
   for (int i = 0; i < 16; ++i) {
     if (lin_exit(ex, t)) {  // the remaining steps are no-ops
       if (COUNT) c.shadow += 16 - i;
@@ -421,7 +465,7 @@ __device__ f3 bounce(const Frame& F, f3 rayDir, f3 pos, f3 normal, f3 color, f3 
       tcol = subs(mk(0.36f, 0.36f, 0.60f), rayDir.y * 0.2f);
     } else {
       if (COUNT) c.lights++;
-      tcol = point_light(F, tcol, normal, pos, &ldist);
+      tcol = point_light<kLean<COUNT>>(F, tcol, normal, pos, &ldist);
     }
     // The weights x / i (glsl:186-187).  For i = 1, 2, 4 the quotient is the
     // real number x * 2^-k, exactly representable unless it underflows, and
@@ -475,10 +519,10 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT h
     if constexpr (wants_hit<HIT>::value) hit(th, id, normal, hcol);
     if (COUNT) c.lights++;
     float ldist;
-    color = point_light(F, hcol, normal, pos, &ldist);
+    color = point_light<kLean<COUNT>>(F, hcol, normal, pos, &ldist);
 #ifdef RM_DBL_LIGHT
     if (!COUNT) {
-      const f3 c2 = point_light(F, hcol, normal, opaque(pos));
+      const f3 c2 = point_light<kLean<COUNT>>(F, hcol, normal, opaque(pos));
       color = mk(vmin(color.x, c2.x), vmin(color.y, c2.y), vmin(color.z, c2.z));
     }
 #endif
@@ -498,6 +542,17 @@ __device__ __forceinline__ f3 render(const Frame& F, f3 ro, f3 rd, Cnt& c, HIT h
 #endif
   return gamma(color);
 }
+
+#ifdef RM_DBL_CAST
+// cost probe: the lane's uv and castRay formed a second time from an opaque copy
+// of its pixel (march doubles its own per-ray set-up)
+__device__ __forceinline__ void dbl_cast(const Frame& F, int px, int py, int s, f3& rd) {
+  asm volatile("" : "+v"(px), "+v"(py));
+  f3 ro2, rd2;
+  cast_ray<kLean<false>>(F, lane_uv(F, 0, px, s), lane_uv(F, 1, py, s), ro2, rd2);
+  rd = mk(vmin(rd.x, rd2.x), vmin(rd.y, rd2.y), vmin(rd.z, rd2.z));
+}
+#endif
 
 // tile_row / tile_col (dispatch order): rm_scene.hpp
 
@@ -523,7 +578,10 @@ __device__ __forceinline__ void pixel_body(const Frame& F, int rowslot, float4* 
   float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f;
   if (py >= 0) {
     f3 ro, rd;
-    cast_ray(F, lane_uv(F, 0, px, -1), lane_uv(F, 1, py, -1), ro, rd);
+    cast_ray<kLean<COUNT>>(F, lane_uv(F, 0, px, -1), lane_uv(F, 1, py, -1), ro, rd);
+#ifdef RM_DBL_CAST
+    if (!COUNT) dbl_cast(F, px, py, -1, rd);
+#endif
     if (COUNT) c.rays++;
     f3 col;
     if constexpr (GBUF) col = render<COUNT, true>(F, ro, rd, c, GbufStore{gbuf + 2 * idx, true});
@@ -535,7 +593,7 @@ __device__ __forceinline__ void pixel_body(const Frame& F, int rowslot, float4* 
   } else if (GBUF) {
     gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
   }
-  store_pixel(F, idx, o0, o1, o2, o3);
+  store_pixel<kLean<COUNT>>(F, idx, o0, o1, o2, o3);
   if (COUNT) {
     F.sdf_counts[idx] = c.march + c.reflect + c.shadow + 4u * c.normals;
     atomicAdd(&F.counters[0], (unsigned long long)c.rays);
@@ -576,7 +634,10 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot, float4*
 #endif
   if (py >= 0) {
     f3 ro, rd;
-    cast_ray(F, lane_uv(F, 0, px, s), lane_uv(F, 1, py, s), ro, rd);
+    cast_ray<kLean<COUNT>>(F, lane_uv(F, 0, px, s), lane_uv(F, 1, py, s), ro, rd);
+#ifdef RM_DBL_CAST
+    if (!COUNT) dbl_cast(F, px, py, s, rd);
+#endif
     if (COUNT) c.rays++;
     if constexpr (GBUF) col = render<COUNT, false>(F, ro, rd, c, GbufStore{gbuf + 2 * idx, s == 0});
     else col = render<COUNT>(F, ro, rd, c);
@@ -621,9 +682,18 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot, float4*
   if (py >= 0) {
     const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3,
                 o2 = ((col.z + b1) + b2) + b3;
-    store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+#ifdef RM_DBL_STORE
+    // cost probe: the AA sum, quantise and pack a second time (store_pixel packs twice)
+    if (!COUNT) {
+      const float p0 = ((opaque(col.x) + r1) + r2) + r3, p1 = ((opaque(col.y) + g1) + g2) + g3,
+                  p2 = ((opaque(col.z) + b1) + b2) + b3;
+      store_pixel<kLean<COUNT>>(F, idx, vmin(o0 / 4.0f, p0 / 4.0f), vmin(o1 / 4.0f, p1 / 4.0f), vmin(o2 / 4.0f, p2 / 4.0f), 1.0f);
+      return;
+    }
+#endif
+    store_pixel<kLean<COUNT>>(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
   } else {
-    store_pixel(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
+    store_pixel<kLean<COUNT>>(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
     if (GBUF) gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
   }
   if (COUNT) F.sdf_counts[idx] = cnt;

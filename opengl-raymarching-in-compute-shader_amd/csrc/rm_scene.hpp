@@ -41,6 +41,9 @@ __device__ __forceinline__ f3 divi(f3 a, int i) { return mk(div_small(a.x, i), d
 // with NaN and +inf passing through unchanged
 __device__ __forceinline__ float len(f3 a) { return sqrt_cr_nonneg(dot(a, a)); }
 __device__ __forceinline__ f3 normalize(f3 a) { return muls(a, rcp_of_sqrt(sqrt_cr_nonneg(dot(a, a)))); }
+// normalize() with the full-range guard of its root behind a wave vote
+// (rm_fastmath.hpp sqrt_vote): the once-per-hit normalisations of the shading
+__device__ __forceinline__ f3 normalize_vote(f3 a) { return muls(a, rcp_of_sqrt(sqrt_vote(dot(a, a)))); }
 // v_min_f32 / v_min3_f32 without the NaN-quieting canonicalisations LLVM adds
 // when it cannot prove an operand canonical (values merged from branches).
 // All operands here are finite sdf values or +inf, never NaN.
@@ -100,6 +103,11 @@ struct Frame {
   int32_t row_block, shard, nshards;
   int32_t row_block0;    // shard 0's rows per round (rm_shard.hpp; = row_block unsharded)
   int32_t rows;          // rows this launch renders (height, or the shard's rows_cap)
+  int32_t light_ball;    // light_in_ball(lpos), formed once per frame on the host with the device's
+                         // own float operations (rm_api.hip make_frame): the shadow exit's
+                         // wave-uniform branch.  It sits in what was padding before the pointers:
+                         // the Frame is a by-value kernel argument, and growing it re-groups the
+                         // scalar loads of every kernel that takes one
   uint8_t* rgba8;        // [rows][width][4] or null
   float* rgba32f;        // [rows][width][4] or null
   uint32_t* sdf_counts;  // [rows][width] or null (counter builds)
@@ -858,9 +866,19 @@ __device__ __forceinline__ float shadow_exit_init(float c, f3 ro, f3 rd, float r
   return a2 > 0.0f ? __builtin_fmaxf(T3, T2) : __builtin_huge_valf();
 }
 // |light - C| <= R_ALL (rounded toward "outside": a light at the boundary keeps the ball)
-__device__ __forceinline__ bool light_in_ball(const Frame& F) {
-  const float ex = F.lpos[0] - SH_CX, ey = F.lpos[1] - SH_CY, ez = F.lpos[2] - SH_CZ;
+// The frame's value is Frame::light_ball: the host evaluates this very function
+// once per frame (rm_api.hip make_frame; IEEE subtract, multiply, add and compare
+// in this order, a NaN or infinite coordinate failing the compare on either
+// side), where every shading wave spent eight VALU on uniform values at each
+// of its shadow call sites.
+__host__ __device__ __forceinline__ bool light_in_ball(const float* lpos) {
+  const float ex = lpos[0] - SH_CX, ey = lpos[1] - SH_CY, ez = lpos[2] - SH_CZ;
   return (ex * ex + ey * ey) + ez * ez <= SH_RALL * SH_RALL * (1.0f - 0x1p-10f);
+}
+template <bool LEAN = false>
+__device__ __forceinline__ bool light_in_ball(const Frame& F) {
+  if (LEAN) return F.light_ball != 0;
+  return light_in_ball(F.lpos);
 }
 __device__ __forceinline__ float miss_exit_init(f3 ro, f3 rd) { return lin_exit_init(MISS_C, 0.0f, ro, rd, ray_rdl(rd)); }
 __device__ __forceinline__ bool lin_exit(float T, float t) { return t > T; }
@@ -966,17 +984,31 @@ __device__ __forceinline__ float gpow(float x, float y) {
 
 // getPointLight glsl:253-276
 // dist_out: length(light - pos), the shadow ray's |rd| (shadow_exit_init).
+// LEAN: the two directions' roots behind sqrt_vote's wave vote (rm_kernels.hip says which
+// kernels take it).
+template <bool LEAN = false>
 __device__ __forceinline__ f3 point_light(const Frame& F, f3 color, f3 normal, f3 pos, float* dist_out = nullptr) {
   f3 lpos = mk(F.lpos[0], F.lpos[1], F.lpos[2]);
   f3 ambient = mk(F.lamb[0], F.lamb[1], F.lamb[2]);
-  f3 viewDir = normalize(sub(pos, mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2])));
-  f3 lightDir = normalize(sub(lpos, pos));
+  f3 viewDir, lightDir;
+  float distance;
+  if (LEAN) {
+    viewDir = normalize_vote(sub(pos, mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2])));
+    // normalize(light - pos) and length(light - pos) share one root, formed once
+    // (rather than left for the compiler to merge across sqrt_vote's branch)
+    const f3 lvec = sub(lpos, pos);
+    distance = sqrt_vote(dot(lvec, lvec));
+    lightDir = muls(lvec, rcp_of_sqrt(distance));
+  } else {
+    viewDir = normalize(sub(pos, mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2])));
+    lightDir = normalize(sub(lpos, pos));
+  }
   float NtoL = gmax(dot(normal, lightDir), 0.0f);
   f3 diffuse = muls(mk(F.ldif[0], F.ldif[1], F.ldif[2]), NtoL);
   f3 reflectDir = reflect(lightDir, normal);
   float spec = gpow(gmax(dot(viewDir, reflectDir), 0.0f), 32.0f);
   f3 specular = muls(mk(F.lspec[0], F.lspec[1], F.lspec[2]), spec);
-  float distance = len(sub(lpos, pos));
+  if (!LEAN) distance = len(sub(lpos, pos));
   if (dist_out) *dist_out = distance;
   float attenuation = rcp_exact((F.lconst + F.llin * distance) + F.lquad * (distance * distance));
   diffuse = muls(diffuse, attenuation);
@@ -1032,21 +1064,44 @@ __device__ __forceinline__ float lane_uv(const Frame& F, int axis, int p, int s)
 }
 
 // castRay glsl:68-74 over vec4 (w included, as the GLSL does).
+// LEAN (rm_kernels.hip says which kernels take it), bit for bit the same rd:
+//   * on frames with Frame::unit_rd (wave-uniform) the w lane is dropped.
+//     unit_rd_check (rm_frame_math.hip) has established that the w of the three
+//     camera vec4s is 0 and that uv, persp and every term are finite, so v[3] =
+//     (uvx 0 + uvy 0) + 0 persp is +-0, its square +0, and (v[2]^2 + 0) is v[2]^2
+//     (a square is never -0).  Other frames add the lane as before;
+//   * the root's full-range guard goes behind sqrt_vote's wave vote, on every
+//     frame; the check's |v|^2 >= 2^-80 (and the float sum within 16 % of it)
+//     makes the vote pass on unit_rd frames.
+// The empty asm keeps the w lane a branch: without it the compiler computes the
+// lane on every frame and selects.  (A branch on unit_rd around the root as
+// well cost k_sample an SGPR spill and a private segment, and the host's product
+// cam_dir[k] persp three more dwords of Frame: LOG.md "fixed work".)
+template <bool LEAN = false>
 __device__ __forceinline__ void cast_ray(const Frame& F, float uvx, float uvy, f3& ro, f3& rd) {
-  float v[4];
+  float v[4], inv;
+  if (LEAN) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (uvx * F.cam_x[k] + uvy * F.cam_y[k]) + F.cam_dir[k] * F.persp;
-  float dd = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  float inv = rcp_of_sqrt(sqrt_cr_nonneg(dd));
+    for (int k = 0; k < 3; ++k) v[k] = (uvx * F.cam_x[k] + uvy * F.cam_y[k]) + F.cam_dir[k] * F.persp;
+    float b = v[2] * v[2];
+    if (!F.unit_rd) {
+      float v3 = (uvx * F.cam_x[3] + uvy * F.cam_y[3]) + F.cam_dir[3] * F.persp;
+      asm volatile("" : "+v"(v3));
+      b = b + v3 * v3;
+    }
+    const float dd = (v[0] * v[0] + v[1] * v[1]) + b;
+    inv = rcp_of_sqrt(sqrt_vote(dd));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = (uvx * F.cam_x[k] + uvy * F.cam_y[k]) + F.cam_dir[k] * F.persp;
+    float dd = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    inv = rcp_of_sqrt(sqrt_cr_nonneg(dd));
+  }
   ro = mk(F.cam_pos[0], F.cam_pos[1], F.cam_pos[2]);
   rd = mk(v[0] * inv, v[1] * inv, v[2] * inv);
 }
 
-// RGBA8 quantization round(clamp(c,0,1)*255), NaN -> 0.
-__device__ __forceinline__ uint32_t quantize(float c) {
-  float v = (c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f;
-  return (uint32_t)(v * 255.0f + 0.5f);
-}
+// quantize (RGBA8, round(clamp(c,0,1)*255), NaN -> 0): rm_fastmath.hpp
 
 // Dispatch order of the tile rows: inside out (the middle row first, then
 // alternately below and above).  The slowest waves (rays grazing the floor near
@@ -1080,16 +1135,24 @@ __device__ __forceinline__ int global_row(const Frame& F, int local_row) {
   return g < F.height ? g : -1;
 }
 
+template <bool LEAN = false>  // quantize<LEAN>
 __device__ __forceinline__ void store_pixel(const Frame& F, size_t idx, float r, float g, float b,
                                             float a) {
   if (F.rgba8) {
     if (F.rgb3) {  // uniform: a scalar branch
       uint8_t* p = F.rgba8 + idx * 3;
-      p[0] = (uint8_t)quantize(r);
-      p[1] = (uint8_t)quantize(g);
-      p[2] = (uint8_t)quantize(b);
+      p[0] = (uint8_t)quantize<LEAN>(r);
+      p[1] = (uint8_t)quantize<LEAN>(g);
+      p[2] = (uint8_t)quantize<LEAN>(b);
     } else {
-      uint32_t w = quantize(r) | (quantize(g) << 8) | (quantize(b) << 16) | (quantize(a) << 24);
+      uint32_t w = quantize<LEAN>(r) | (quantize<LEAN>(g) << 8) | (quantize<LEAN>(b) << 16) | (quantize<LEAN>(a) << 24);
+#ifdef RM_DBL_STORE
+      {  // cost probe: quantise and pack a second time from opaque copies
+        float r2 = r, g2 = g, b2 = b;
+        asm volatile("" : "+v"(r2), "+v"(g2), "+v"(b2));
+        w &= quantize<LEAN>(r2) | (quantize<LEAN>(g2) << 8) | (quantize<LEAN>(b2) << 16) | (quantize<LEAN>(a) << 24);
+      }
+#endif
       reinterpret_cast<uint32_t*>(F.rgba8)[idx] = w;
     }
   }

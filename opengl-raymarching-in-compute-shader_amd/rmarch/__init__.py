@@ -666,6 +666,16 @@ class Renderer:
         _check(lib().rm_get_uniforms(self._h, C.byref(u)), self._h)
         return u
 
+    def debug_frame_flags(self) -> dict:
+        """Diagnostic (rm_debug_frame_flags; not part of rm_api.h, bound on first use): the
+        wave-uniform branches a frame of the current uniforms takes, as the host sets them:
+        Frame::unit_rd and Frame::light_ball."""
+        fn = lib().rm_debug_frame_flags
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+        out = (C.c_int32 * 2)()
+        _check(fn(self._h, out), self._h)
+        return {"unit_rd": int(out[0]), "light_ball": int(out[1])}
+
     # -- dispatch / barrier / readback
     def dispatch(self, u: Optional[rm_uniforms] = None) -> None:
         """glDispatchCompute (main.cpp:123): asynchronous."""

@@ -4,6 +4,9 @@
 #   tools/build_variant.sh NAME --rev GITREV    -> librm built from a committed revision
 #   tools/build_variant.sh NAME --patch F.diff  -> librm built with a patch applied
 #   KOPT=-O3 tools/build_variant.sh NAME         -> the built-in kernels at another -O level
+# Cost probes (a phase run twice, rm_kernels.hip): -DRM_DBL_MARCH, _BMARCH, _NORMAL, _SHADOW,
+# _LIGHT, _GAMMA, _CAST (uv, castRay and the primary march's per-ray set-up) and _STORE (the
+# AA sum, quantise and pack); -DRM_STATS=1 builds the counters of tools/stats_probe.py.
 #                                                 (experiments live as patches, not knobs)
 set -e
 name=$1; shift
@@ -28,18 +31,28 @@ done
 # rm_kernels.hip as the Makefile builds it (both objects without SLP; RM_PIXEL_SLP=1
 # builds k_pixel with it, the round-3 flags), except
 # for the RM_STATS build, whose counters must live in one code object
+for d in "$@"; do  # a misspelt probe would silently time the plain build
+  case "$d" in
+    -DRM_DBL_*) case "${d%%=*}" in
+        -DRM_DBL_MARCH|-DRM_DBL_BMARCH|-DRM_DBL_NORMAL|-DRM_DBL_SHADOW|-DRM_DBL_LIGHT|-DRM_DBL_GAMMA|-DRM_DBL_CAST|-DRM_DBL_STORE) ;;
+        *) echo "build_variant: unknown cost probe $d" >&2; exit 1 ;;
+      esac ;;
+  esac
+done
 case "$*" in
   *RM_STATS*) /opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" & ;;
-  *) pslp=-fno-slp-vectorize; [ -n "$RM_PIXEL_SLP" ] && pslp=-fslp-vectorize
+  *) lean=-DRM_LEAN_FIXED_WORK=1; case "$*" in *RM_LEAN_FIXED_WORK*) lean=;; esac  # as the Makefile, unless given
+     grep -q RM_LEAN_FIXED_WORK "$src/$pkg/csrc/rm_kernels.hip" || lean=
+     pslp=-fno-slp-vectorize; [ -n "$RM_PIXEL_SLP" ] && pslp=-fslp-vectorize
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} $pslp -DRM_KERNELS_PIXEL_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" &
-     /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
+     /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY $lean -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
 esac
 # the ray-query, G-buffer, SDF-query, adaptive and mesh kernels, as the Makefile builds them
 # (absent in older revisions)
-for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges rm_mesh; do
+for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges rm_mesh rm_pattern; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
-for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive; do
+for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags -fno-slp-vectorize -mllvm -amdgpu-inline-max-bb=8000 -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
 /opt/rocm/bin/hipcc $flags -x c++ -c "$src/$pkg/csrc/rm_host.cpp" -o "$b/rm_host.o" &

@@ -4,11 +4,15 @@
 // correctly-rounded operation (HIP default -fhip-fp32-correctly-rounded-divide-sqrt).
 //   sqrt candidates: all non-negative finite floats (0x00000000..0x7f7fffff)
 //   x / C candidates: all finite floats, for the capsule constant C = dot(ba, ba)
+// Modes of their own (argv[1]), each over all 2^32 bit patterns:
+//   quantize   rm_fastmath.hpp quantize<true> (the v_med3 clamp) against the compare-and-select form
+//   sqrt_vote  sqrt_vote against sqrt_cr_nonneg, bitwise, with the wave vote going both ways
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/exhaustive_fp.hip -o tools/exhaustive_fp
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../opengl-raymarching-in-compute-shader_amd/csrc/rm_fastmath.hpp"
 
@@ -174,13 +178,81 @@ __global__ void k_div_small(unsigned long long* cnt, unsigned* first) {
   for (int k = 0; k < 4; ++k) atomicAdd(&cnt[k], c[k]);
 }
 
-int main() {
+// quantize (v_med3 clamp) against round(clamp(c, 0, 1) * 255) written with compares
+// and selects, NaN -> 0: every bit pattern.
+__device__ __forceinline__ unsigned quantize_select(float c) {
+  const float v = (c > 0.0f) ? ((c < 1.0f) ? c : 1.0f) : 0.0f;
+  return (unsigned)(v * 255.0f + 0.5f);
+}
+__global__ void k_quantize(unsigned long long* bad, unsigned* first) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < 0x100000000ull;
+       i += (unsigned long long)gridDim.x * blockDim.x) {
+    float x = __uint_as_float((unsigned)i);
+    asm volatile("" : "+v"(x));  // the kernels quantise register values, not constants
+    const unsigned a = rmd::quantize<true>(x), b = quantize_select(x);
+    if (a != b || a > 255u) {
+      atomicAdd(&bad[0], 1ull);
+      atomicMin(&first[0], (unsigned)i);
+    }
+    if (x != x && a != 0u) atomicAdd(&bad[1], 1ull);
+  }
+}
+
+// sqrt_vote against sqrt_cr_nonneg, bitwise, on every bit pattern.  A wave holds 64
+// consecutive patterns, and 2^-96 = 0x0f800000 is a multiple of 64: in the plain pass
+// every wave votes one way (sqrt_core alone for x >= 2^-96).  The mixed pass puts
+// 2^-100 into lane 0 of every wave, so every x >= 2^-96 also goes through a vote
+// that fails.
+__global__ void k_sqrt_vote(unsigned long long* bad, unsigned* first, int mixed) {
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < 0x100000000ull;
+       i += (unsigned long long)gridDim.x * blockDim.x) {
+    float x = __uint_as_float((unsigned)i);
+    if (mixed && (threadIdx.x & 63) == 0) x = 0x1p-100f;
+    const float a = rmd::sqrt_vote(x), b = rmd::sqrt_cr_nonneg(x);
+    if (__float_as_uint(a) != __float_as_uint(b)) {
+      atomicAdd(&bad[mixed ? 1 : 0], 1ull);
+      atomicMin(&first[mixed ? 1 : 0], (unsigned)i);
+    }
+    // how many patterns took sqrt_core alone (the vote passed)
+    if (__all(x >= rmd::SQRT_CORE_MIN)) atomicAdd(&bad[2 + (mixed ? 1 : 0)], 1ull);
+  }
+}
+
+int main(int argc, char** argv) {
   unsigned long long* bad;
   unsigned* first;
   CK(hipMalloc(&bad, 4 * sizeof(unsigned long long)));
   CK(hipMalloc(&first, 4 * sizeof(unsigned)));
   CK(hipMemset(bad, 0, 4 * sizeof(unsigned long long)));
   CK(hipMemset(first, 0xff, 4 * sizeof(unsigned)));
+  if (argc > 1 && !strcmp(argv[1], "quantize")) {
+    hipLaunchKernelGGL(k_quantize, dim3(4096), dim3(256), 0, 0, bad, first);
+    CK(hipDeviceSynchronize());
+    unsigned long long qb[4];
+    unsigned qf[4];
+    CK(hipMemcpy(qb, bad, sizeof qb, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(qf, first, sizeof qf, hipMemcpyDeviceToHost));
+    printf("quantize  med3 form against compare-and-select on all 2^32 inputs: %llu mismatches (first 0x%08x)\n", qb[0], qf[0]);
+    printf("quantize  NaN inputs not giving 0: %llu\n", qb[1]);
+    return (qb[0] == 0 && qb[1] == 0) ? 0 : 1;
+  }
+  if (argc > 1 && !strcmp(argv[1], "sqrt_vote")) {
+    for (int mixed = 0; mixed < 2; ++mixed) {
+      hipLaunchKernelGGL(k_sqrt_vote, dim3(4096), dim3(256), 0, 0, bad, first, mixed);
+      CK(hipDeviceSynchronize());
+    }
+    unsigned long long vb[4];
+    unsigned vf[4];
+    CK(hipMemcpy(vb, bad, sizeof vb, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(vf, first, sizeof vf, hipMemcpyDeviceToHost));
+    printf("sqrt_vote  against sqrt_cr_nonneg on all 2^32 inputs, waves of 64 consecutive patterns: %llu mismatches (first 0x%08x), %llu inputs by sqrt_core alone\n", vb[0], vf[0], vb[2]);
+    printf("sqrt_vote  the same with 2^-100 in lane 0 of every wave: %llu mismatches (first 0x%08x), %llu inputs by sqrt_core alone\n", vb[1], vf[1], vb[3]);
+    return (vb[0] == 0 && vb[1] == 0 && vb[2] > 0 && vb[3] == 0) ? 0 : 1;
+  }
+  if (argc > 1) {
+    fprintf(stderr, "usage: exhaustive_fp [quantize | sqrt_vote]\n");
+    return 2;
+  }
   hipLaunchKernelGGL(k_sqrt, dim3(4096), dim3(256), 0, 0, bad, first);
   CK(hipDeviceSynchronize());
   unsigned long long hb[4];

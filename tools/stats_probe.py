@@ -46,6 +46,9 @@ print("lazy block rate: waves %.3f lanes %.3f" % (h[9] / h[8], h[41] / h[40]))
 print("primary rays: %d misses, %.1f steps each; %d hits, %.1f steps each"
       % (h[3], h[4] / max(h[3], 1), h[23], h[5] / max(h[23], 1)))
 print("reflected: lane steps of misses %d, of hits %d" % (h[24], h[25]))
+print("general-loop wave steps with only downward lanes left at the segment's start: primary %d after step 16, "
+      "%d after step 64 (of %d primary wave steps); reflected %d after step 16, %d after step 64 (of %d)"
+      % (h[35], h[36], h[15], h[55], h[56], h[6]))
 print("clearance: plane-only normals %.3f of the normal waves (%.3f of their lanes); shadow step 0 %.3f, "
       "step 1 %.3f of the shadow waves (%.3f, %.3f of their lanes)"
       % (h[21] / max(h[27], 1), h[53] / max(h[59], 1), h[22] / max(h[29], 1), h[28] / max(h[29], 1),
