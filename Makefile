@@ -28,10 +28,11 @@ DRIVER   := $(PKG)/rm_frameloop
 RM_OBJS  := rm_api rm_api_comm rm_api_graph rm_frame_math rm_kernels rm_kernels_aa rm_table rm_jit rm_host rm_comm \
             rm_api_trace rm_trace rm_table_trace rm_api_gbuffer rm_gbuffer rm_table_gbuffer \
             rm_api_sdf rm_sdf rm_table_sdf rm_api_adaptive rm_adaptive rm_table_adaptive rm_adaptive_edges \
-            rm_api_mesh rm_mesh rm_api_query rm_api_pattern rm_pattern rm_table_pattern
+            rm_api_mesh rm_mesh rm_api_query rm_api_pattern rm_pattern rm_table_pattern \
+            rm_adaptive_pattern rm_table_adaptive_pattern
 RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
             $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_builtin_fast.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
-            $(CSRC)/rm_mesh_args.hpp $(CSRC)/rm_pattern_args.hpp \
+            $(CSRC)/rm_mesh_args.hpp $(CSRC)/rm_pattern_args.hpp $(CSRC)/rm_adaptive_pattern.hpp \
             include/rm_api.h Makefile
 # The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
 # the names they #include each other by.
@@ -74,13 +75,13 @@ $(PKG)/build/rm_table.o: $(CSRC)/rm_table.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-# The query and output families (DESIGN §4.9-§4.14) in objects of their own, so
+# The query and output families (DESIGN §4.9-§4.15) in objects of their own, so
 # that rm_kernels.o / rm_kernels_aa.o / rm_table.o are what they are without
 # them.  The built-in scene's (ray queries, the G-buffer frame kernels, SDF field
-# queries, adaptive supersampling, sample-pattern frames) include the render kernels' source for its
+# queries, adaptive supersampling, sample-pattern frames, pattern refinement) include the render kernels' source for its
 # device code alone and take that source's flags; the scene-independent ones
 # (the geometry-edge classifier, mesh extraction) take the same flags.
-BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive rm_pattern
+BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive rm_pattern rm_adaptive_pattern
 PLAIN_FAMS   := rm_adaptive_edges rm_mesh
 $(BUILTIN_FAMS:%=$(PKG)/build/%.o): $(CSRC)/rm_kernels.hip
 $(BUILTIN_FAMS:%=$(PKG)/build/%.o) $(PLAIN_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
@@ -94,7 +95,8 @@ $(BUILTIN_FAMS:%=$(PKG)/build/%.o) $(PLAIN_FAMS:%=$(PKG)/build/%.o): $(PKG)/buil
 # Table and its result through scratch memory (432 B per lane; none with the cap
 # raised).
 TRACE_INLINE := -mllvm -amdgpu-inline-max-bb=8000
-TABLE_FAMS   := rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern
+TABLE_FAMS   := rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern \
+                rm_table_adaptive_pattern
 $(TABLE_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(CSRC)/rm_table.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@

@@ -83,6 +83,15 @@ inline int dispatchPattern(rm_ctx* p, int preset = RM_PATTERN_GRID2) {
   return rc != RM_OK ? rc : rm_dispatch_pattern(p, &s);
 }
 inline int dispatchPattern(rm_ctx* p, const rm_sample_pattern& pattern) { return rm_dispatch_pattern(p, &pattern); }
+// dispatchAdaptiveEdges with a preset pattern's samples on the flagged pixels
+// (rm_dispatch_adaptive_pattern; the default, GRID4: sixteen centred samples on the edges)
+inline int dispatchAdaptivePattern(rm_ctx* p, int preset = RM_PATTERN_GRID4, const rm_aa_criteria* criteria = nullptr) {
+  rm_aa_criteria c;
+  if (!criteria) rm_aa_criteria_init(&c);
+  rm_sample_pattern s;
+  const int rc = rm_sample_pattern_init(&s, preset);
+  return rc != RM_OK ? rc : rm_dispatch_adaptive_pattern(p, criteria ? criteria : &c, &s);
+}
 inline int memoryBarrier(rm_ctx* p) { return rm_synchronize(p); }
 
 }  // namespace rm

@@ -668,7 +668,8 @@ int rm_get_output_gbuffer(rm_ctx *ctx, void **device_ptr);
  *    pixel bit for bit in RGBA32F and byte for byte in RGBA8.
  *  - The reference's AA samples sit at +0.125 .. +1 pixel from the pixel's centre
  *    ray, not around it: a refined pixel is the reference's AA pixel with that
- *    shift.  These calls do not re-centre it.
+ *    shift.  These calls do not re-centre it (rm_dispatch_adaptive_pattern and
+ *    rm_dispatch_refine_pattern below refine with a centred pattern).
  *  - u.AA is ignored and the context's uniforms stay as they are; bounceVar,
  *    shadow_mode, iTime, the light and the camera apply as in rm_dispatch.
  *  - Afterwards the context reads as after an rm_dispatch (rm_read_rgba8 /
@@ -821,7 +822,8 @@ int rm_dispatch_adaptive_edges(rm_ctx *ctx, const rm_aa_criteria *criteria);
  *    renders, as the adaptive refinement does: same values).  RM_ERR_STATE on a
  *    context with counters, nshards > 1, a communicator, ngpus >= 1,
  *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay, no
- *    pattern refinement in the adaptive calls, no accumulation across calls. */
+ *    accumulation across calls.  (Pattern refinement in the adaptive calls: the
+ *    next section.) */
 #define RM_HAS_SAMPLE_PATTERN 1
 #define RM_MAX_SAMPLES 16
 #define RM_PATTERN_CUMULATIVE 1u      /* flags: offsets are increments, the GLSL's x += o / W */
@@ -849,6 +851,59 @@ int rm_pattern_uv_table(const rm_sample_pattern *p, int32_t width, int32_t heigh
 /* The frame of the pattern.  RM_ERR_INVALID for a null context or pattern
  * (nothing written) or an invalid pattern.  Asynchronous. */
 int rm_dispatch_pattern(rm_ctx *ctx, const rm_sample_pattern *p);
+
+/* ---- pattern refinement: the adaptive calls with a sample pattern's samples ------
+ * An extension that joins the two above.  The frame of these calls is the AA-off
+ * frame with every FLAGGED pixel replaced by that pixel of the frame
+ * rm_dispatch_pattern(ctx, pattern) would render with the same uniforms and scene.
+ * Every pixel is therefore exactly one of two values defined above: pass 1's
+ * pixel (the centre ray), or the sample-pattern rule's pixel (uv from
+ * rm_pattern_uv_table, c_s a SHADE trace, sum = c_0, sum = sum + c_s in order,
+ * / (float)n, alpha 1, the usual RGBA8 quantisation), bit for bit in RGBA32F and
+ * byte for byte in RGBA8.  With a centred pattern a refined pixel registers with
+ * the G-buffer record of its centre ray, which the reference's shifted samples of
+ * rm_dispatch_adaptive_edges do not.
+ *
+ *  - Three anchors follow.  RM_PATTERN_REFERENCE gives rm_dispatch_adaptive_edges'
+ *    (or rm_dispatch_refine's) frame.  One sample at (0, 0) gives the AA-off frame
+ *    whatever is flagged.  An all-ones mask gives the rm_dispatch_pattern frame.
+ *  - Flagging, rm_dispatch_adaptive_pattern: rm_dispatch_adaptive_edges' rule, word
+ *    for word, with its validation of the criteria, its context requirements (the
+ *    geometric criteria need RM_OUT_GBUFFER, the context a colour output) and its
+ *    order of checks.  COLOR alone works on plain contexts, so the call covers
+ *    rm_dispatch_adaptive's rule too.
+ *  - Flagging, rm_dispatch_refine_pattern / _device: rm_dispatch_refine's rule (a
+ *    non-zero byte flags, row_pitch 0 = width, the device mask may be the
+ *    context's own copy).  Unlike rm_dispatch_refine they admit G-buffer contexts
+ *    (a G-buffer criterion of the caller's own); pass 1 then writes the records,
+ *    as in rm_dispatch_adaptive_edges.
+ *  - Afterwards the context reads as after rm_dispatch_adaptive_edges: on a
+ *    G-buffer context the G-buffer holds pass 1's records for every pixel, and
+ *    rm_read_aa_mask, rm_get_aa_mask and rm_aa_refined serve the call.  Nothing is
+ *    sticky, u.AA is ignored and the uniforms stay.  With rm_enable_timing one
+ *    event pair brackets pass 1 through the refinement, one launch of one frame;
+ *    the pattern's uv table, which these calls share with rm_dispatch_pattern (a
+ *    repeated pattern uploads nothing, across both kinds of call), is uploaded
+ *    before the pair.
+ *  - Errors: RM_ERR_INVALID for a null context (nothing is touched), for a null or
+ *    invalid pattern (the sample patterns' validation, the reason in rm_last_error
+ *    after the call's name), and for the criteria or the mask as in the calls
+ *    above.  RM_ERR_STATE, naming the call, on a context with counters, nshards >
+ *    1, a communicator, ngpus >= 1 or rm_graph_enable on.
+ *  - RM_AA_REFINE_WAVES overrides the refinement's grid as above; without it a
+ *    pattern of one sample, whose wave takes 64 list entries instead of 16, gets
+ *    min(ceil(W H / 64), 128 x compute units) workgroups.
+ *  - Out of scope in this version: batches, graph replay, shards,
+ *    hiprtc-specialised refine kernels (the generic table code refines, same
+ *    values), accumulation across calls. */
+#define RM_HAS_ADAPTIVE_PATTERN 1
+/* rm_dispatch_adaptive_edges with `pattern`'s samples on the flagged pixels.  Asynchronous. */
+int rm_dispatch_adaptive_pattern(rm_ctx *ctx, const rm_aa_criteria *criteria, const rm_sample_pattern *pattern);
+/* rm_dispatch_refine / _device with `pattern`'s samples on the flagged pixels; the
+ * host mask is uploaded synchronously, the frame is asynchronous. */
+int rm_dispatch_refine_pattern(rm_ctx *ctx, const uint8_t *mask, size_t row_pitch, const rm_sample_pattern *pattern);
+int rm_dispatch_refine_pattern_device(rm_ctx *ctx, const void *mask_dev, size_t row_pitch,
+                                      const rm_sample_pattern *pattern);
 
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process

@@ -166,9 +166,10 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
 // frames only).
 const SceneKernels& rm::scene_kernels(const rm_ctx* c) {
   static const SceneKernels builtin{launch_trace, launch_sdf_points, launch_sdf_grid, launch_adapt_refine,
-                                    launch_pattern};
+                                    launch_pattern, launch_adapt_refine_pattern};
   static const SceneKernels table{launch_table_trace, launch_table_sdf_points, launch_table_sdf_grid,
-                                  launch_table_adapt_refine, launch_table_pattern};
+                                  launch_table_adapt_refine, launch_table_pattern,
+                                  launch_table_adapt_refine_pattern};
   return c->nprims ? table : builtin;
 }
 

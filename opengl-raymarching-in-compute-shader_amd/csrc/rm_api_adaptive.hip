@@ -1,7 +1,9 @@
 // rm_api_adaptive.hip — librm's C-ABI for adaptive supersampling (include/rm_api.h
-// RM_HAS_ADAPTIVE_AA, RM_HAS_ADAPTIVE_EDGES): rm_dispatch_adaptive,
-// rm_dispatch_adaptive_edges, rm_dispatch_refine / _device, and the mask and the
-// count of the last such dispatch.
+// RM_HAS_ADAPTIVE_AA, RM_HAS_ADAPTIVE_EDGES, RM_HAS_ADAPTIVE_PATTERN; DESIGN.md §4.12,
+// §4.15): rm_dispatch_adaptive, rm_dispatch_adaptive_edges, rm_dispatch_refine /
+// _device, their pattern forms rm_dispatch_adaptive_pattern and
+// rm_dispatch_refine_pattern / _device, and the mask and the count of the last such
+// dispatch.
 //
 // One such dispatch is, on the context's stream: pass 1 (the kernel rm_dispatch
 // would launch for the frame with AA off; on a G-buffer context the G-buffer
@@ -10,14 +12,17 @@
 // caller's edge criteria on pass 1's G-buffer and / or image), their scan and
 // list, and the refinement of the listed pixels (rm_adaptive.hip for the built-in
 // scene, rm_table_adaptive.hip for a table), which writes colour only.  The host
-// never learns the count.
+// never learns the count.  The pattern forms refine at the offsets of a caller's
+// sample pattern instead (rm_adaptive_pattern.hip, rm_table_adaptive_pattern.hip),
+// from rm_dispatch_pattern's uv table (rm_api_pattern.hip ensure_table), uploaded
+// before pass 1 when the pattern is not the last call's.
 //
 // This version: one-device, whole-frame contexts.  Out of scope, and refused:
 // sharded, communicator and multi-device contexts (a pixel's neighbour may live
 // on another rank), counting contexts, batches and graph replay; G-buffer
-// contexts for every call but rm_dispatch_adaptive_edges and the mask's and the
-// count's readers; hiprtc-specialised refine kernels (the generic table code
-// refines).
+// contexts for every call but rm_dispatch_adaptive_edges, the pattern forms and the
+// mask's and the count's readers; hiprtc-specialised refine kernels (the generic
+// table code refines).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +33,7 @@
 #include <string>
 
 #include "rm_ctx.hpp"
+#include "rm_frame_math.hpp"
 
 using namespace rm;
 
@@ -85,10 +91,11 @@ int ensure_buffers(rm_ctx* c) {
 // striding further each (4K cfg3 frames at threshold 8, alone on the device:
 // 1.04 ms at 32 per unit, 0.99 at 64, 0.85 at 128, 0.86 at 65535 waves;
 // profiles/adaptive_probe.txt).
+// per: the list entries of a group, 16, or 64 for a pattern of one sample.
 constexpr size_t kRefineWavesPerCU = 128;
-int refine_waves(const rm_ctx* c) {
+int refine_waves(const rm_ctx* c, size_t per = 16) {
   if (c->aa_waves_env) return c->aa_waves_env;
-  const size_t groups = ((size_t)c->cfg.width * (size_t)c->cfg.height + 15) / 16;
+  const size_t groups = ((size_t)c->cfg.width * (size_t)c->cfg.height + per - 1) / per;
   return (int)std::min(groups, (size_t)c->aa_cus * kRefineWavesPerCU);
 }
 
@@ -102,10 +109,15 @@ bool edges_naive() {
 
 // One adaptive frame.  The flags: the caller's edge criteria `cr`; else a device
 // mask mask_src at mask_pitch; else (both null) colour contrast at `threshold`.
+// The refinement: the reference's four samples, or with `pat` (valid) that
+// pattern's, for the call `call`.
 int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int threshold,
-                   const rm_aa_criteria* cr = nullptr) {
+                   const rm_aa_criteria* cr = nullptr, const rm_sample_pattern* pat = nullptr,
+                   const char* call = nullptr) {
   int rc;
   if ((rc = order_after_batch(c)) != RM_OK) return rc;
+  // (the table's upload, when there is one, before the timed pair)
+  if (pat && (rc = ensure_table(c, *pat, call)) != RM_OK) return rc;
   rmd::Frame F = make_frame(c);
   F.aa = 0;  // pass 1 is the AA-off frame whatever u.AA says; the uniforms stay
   rm::pixel_grid(F.width, F.rows, false, &F.grid_x, &F.grid_y);
@@ -133,7 +145,20 @@ int adaptive_frame(rm_ctx* c, const void* mask_src, size_t mask_pitch, int thres
     e = launch_adapt_flags(F, A, mask_src, mask_pitch, threshold, c->stream);
   }
   if (e != hipSuccess) return hip_fail(c, e, "adaptive flag launch");
-  e = scene_kernels(c).adapt_refine(F, A, refine_waves(c), c->stream);
+  if (pat) {
+    // |rd| = 1 over the range of this pattern's uv: pass 1's unit_rd (make_frame's) is
+    // proved for the centre rays and the reference offsets only
+    rmd::Frame R = F;
+    R.unit_rd = unit_rd_check(c->u.camera, F.persp, c->pat_lo, c->pat_hi) ? 1 : 0;
+    rmd::PatternArgs P;
+    P.uvx = static_cast<const float*>(c->pat_uv.p);
+    P.uvy = P.uvx + (size_t)c->cfg.width * (size_t)pat->n;
+    P.n = pat->n;
+    P.nf = (float)pat->n;
+    e = scene_kernels(c).adapt_refine_pattern(R, A, P, refine_waves(c, pat->n == 1 ? 64 : 16), c->stream);
+  } else {
+    e = scene_kernels(c).adapt_refine(F, A, refine_waves(c), c->stream);
+  }
   if (e != hipSuccess) return hip_fail(c, e, "adaptive refine launch");
   if ((rc = phase(c, 1)) != RM_OK) return rc;
   if ((rc = t.end(c)) != RM_OK) return rc;
@@ -155,11 +180,48 @@ int begin(rm_ctx* c, const char* call, bool gbuf_ok = false) {
   return ensure_buffers(c);
 }
 
+// A context with RM_OUT_GBUFFER and no colour output has nothing to refine.
+int check_colour(rm_ctx* c, const char* call) {
+  if (!(c->cfg.outputs & (RM_OUT_RGBA8 | RM_OUT_RGBA32F)))
+    return fail(c, RM_ERR_STATE, std::string(call) + ": the context has no colour output to refine");
+  return RM_OK;
+}
+
 int check_mask(rm_ctx* c, const char* call, const void* mask, size_t* row_pitch) {
   if (!mask) return fail(c, RM_ERR_INVALID, std::string(call) + ": null mask");
   if (*row_pitch == 0) *row_pitch = (size_t)c->cfg.width;
   if (*row_pitch < (size_t)c->cfg.width)
     return fail(c, RM_ERR_INVALID, std::string(call) + ": row_pitch smaller than a row");
+  return RM_OK;
+}
+
+// The checks of rm_dispatch_adaptive_edges' criteria, in its order, for `call`: the
+// fields' ranges (RM_ERR_INVALID), then what the selected criteria and the refinement
+// need of the context (RM_ERR_STATE).
+int check_criteria(rm_ctx* c, const char* call, const rm_aa_criteria* cr) {
+  const std::string who = std::string(call) + ": ";
+  if (!cr) return fail(c, RM_ERR_INVALID, who + "null criteria");
+  if (cr->struct_size != sizeof(rm_aa_criteria))
+    return fail(c, RM_ERR_INVALID, who + "rm_aa_criteria.struct_size is not sizeof(rm_aa_criteria)");
+  constexpr uint32_t kGeometry = RM_AA_EDGE_ID | RM_AA_EDGE_DEPTH | RM_AA_EDGE_NORMAL | RM_AA_EDGE_ALBEDO;
+  if (cr->edges == 0 || (cr->edges & ~(kGeometry | RM_AA_EDGE_COLOR)))
+    return fail(c, RM_ERR_INVALID, who + "edges must be a non-empty mask of RM_AA_EDGE_* bits");
+  if ((cr->edges & RM_AA_EDGE_COLOR) && (cr->color_threshold < 0 || cr->color_threshold > 255))
+    return fail(c, RM_ERR_INVALID, who + "color_threshold must be in 0..255");
+  // (written so that a NaN fails)
+  if ((cr->edges & RM_AA_EDGE_DEPTH) && !(cr->depth_rel >= 0.0f))
+    return fail(c, RM_ERR_INVALID, who + "depth_rel must be >= 0 (+inf allowed)");
+  if ((cr->edges & RM_AA_EDGE_NORMAL) && !(cr->normal_cos >= -1.0f && cr->normal_cos <= 1.0f))
+    return fail(c, RM_ERR_INVALID, who + "normal_cos must be in [-1, 1]");
+  if ((cr->edges & kGeometry) && !has_gbuf(c))
+    return fail(c, RM_ERR_STATE, who + "the ID, DEPTH, NORMAL and ALBEDO criteria need RM_OUT_GBUFFER in rm_config.outputs");
+  return check_colour(c, call);
+}
+
+// RM_ERR_INVALID, naming `call`, with rm::pattern_invalid's reason for a null or invalid pattern.
+int check_pattern(rm_ctx* c, const char* call, const rm_sample_pattern* p) {
+  if (!p) return fail(c, RM_ERR_INVALID, std::string(call) + ": null pattern");
+  if (const char* why = pattern_invalid(p)) return fail(c, RM_ERR_INVALID, std::string(call) + ": " + why);
   return RM_OK;
 }
 
@@ -188,27 +250,20 @@ int rm_aa_criteria_init(rm_aa_criteria* cr) {
 
 int rm_dispatch_adaptive_edges(rm_ctx* c, const rm_aa_criteria* cr) {
   if (!c) return RM_ERR_INVALID;
-  const std::string who = "rm_dispatch_adaptive_edges: ";
-  if (!cr) return fail(c, RM_ERR_INVALID, who + "null criteria");
-  if (cr->struct_size != sizeof(rm_aa_criteria))
-    return fail(c, RM_ERR_INVALID, who + "rm_aa_criteria.struct_size is not sizeof(rm_aa_criteria)");
-  constexpr uint32_t kGeometry = RM_AA_EDGE_ID | RM_AA_EDGE_DEPTH | RM_AA_EDGE_NORMAL | RM_AA_EDGE_ALBEDO;
-  if (cr->edges == 0 || (cr->edges & ~(kGeometry | RM_AA_EDGE_COLOR)))
-    return fail(c, RM_ERR_INVALID, who + "edges must be a non-empty mask of RM_AA_EDGE_* bits");
-  if ((cr->edges & RM_AA_EDGE_COLOR) && (cr->color_threshold < 0 || cr->color_threshold > 255))
-    return fail(c, RM_ERR_INVALID, who + "color_threshold must be in 0..255");
-  // (written so that a NaN fails)
-  if ((cr->edges & RM_AA_EDGE_DEPTH) && !(cr->depth_rel >= 0.0f))
-    return fail(c, RM_ERR_INVALID, who + "depth_rel must be >= 0 (+inf allowed)");
-  if ((cr->edges & RM_AA_EDGE_NORMAL) && !(cr->normal_cos >= -1.0f && cr->normal_cos <= 1.0f))
-    return fail(c, RM_ERR_INVALID, who + "normal_cos must be in [-1, 1]");
-  if ((cr->edges & kGeometry) && !has_gbuf(c))
-    return fail(c, RM_ERR_STATE, who + "the ID, DEPTH, NORMAL and ALBEDO criteria need RM_OUT_GBUFFER in rm_config.outputs");
-  if (!(c->cfg.outputs & (RM_OUT_RGBA8 | RM_OUT_RGBA32F)))
-    return fail(c, RM_ERR_STATE, who + "the context has no colour output to refine");
-  const int rc = begin(c, "rm_dispatch_adaptive_edges", true);
+  int rc = check_criteria(c, "rm_dispatch_adaptive_edges", cr);
   if (rc != RM_OK) return rc;
+  if ((rc = begin(c, "rm_dispatch_adaptive_edges", true)) != RM_OK) return rc;
   return adaptive_frame(c, nullptr, 0, 0, cr);
+}
+
+int rm_dispatch_adaptive_pattern(rm_ctx* c, const rm_aa_criteria* cr, const rm_sample_pattern* p) {
+  if (!c) return RM_ERR_INVALID;
+  const char* call = "rm_dispatch_adaptive_pattern";
+  int rc = check_pattern(c, call, p);
+  if (rc != RM_OK) return rc;
+  if ((rc = check_criteria(c, call, cr)) != RM_OK) return rc;
+  if ((rc = begin(c, call, true)) != RM_OK) return rc;
+  return adaptive_frame(c, nullptr, 0, 0, cr, p, call);
 }
 
 int rm_dispatch_refine(rm_ctx* c, const uint8_t* mask, size_t row_pitch) {
@@ -233,10 +288,38 @@ int rm_dispatch_refine_device(rm_ctx* c, const void* mask_dev, size_t row_pitch)
   return adaptive_frame(c, mask_dev, row_pitch, 0);
 }
 
+int rm_dispatch_refine_pattern(rm_ctx* c, const uint8_t* mask, size_t row_pitch, const rm_sample_pattern* p) {
+  if (!c) return RM_ERR_INVALID;
+  const char* call = "rm_dispatch_refine_pattern";
+  int rc = check_pattern(c, call, p);
+  if (rc != RM_OK) return rc;
+  if ((rc = check_mask(c, call, mask, &row_pitch)) != RM_OK) return rc;
+  if ((rc = check_colour(c, call)) != RM_OK) return rc;
+  if ((rc = begin(c, call, true)) != RM_OK) return rc;
+  // the upload of rm_dispatch_refine
+  const size_t w = (size_t)c->cfg.width;
+  RM_HIP(c, hipMemcpy2DAsync(c->d_aa_mask, w, mask, row_pitch, w, (size_t)c->cfg.height, hipMemcpyHostToDevice,
+                             c->stream));
+  RM_HIP(c, hipStreamSynchronize(c->stream));
+  return adaptive_frame(c, c->d_aa_mask, w, 0, nullptr, p, call);
+}
+
+int rm_dispatch_refine_pattern_device(rm_ctx* c, const void* mask_dev, size_t row_pitch,
+                                      const rm_sample_pattern* p) {
+  if (!c) return RM_ERR_INVALID;
+  const char* call = "rm_dispatch_refine_pattern_device";
+  int rc = check_pattern(c, call, p);
+  if (rc != RM_OK) return rc;
+  if ((rc = check_mask(c, call, mask_dev, &row_pitch)) != RM_OK) return rc;
+  if ((rc = check_colour(c, call)) != RM_OK) return rc;
+  if ((rc = begin(c, call, true)) != RM_OK) return rc;
+  return adaptive_frame(c, mask_dev, row_pitch, 0, nullptr, p, call);
+}
+
 int rm_read_aa_mask(rm_ctx* c, uint8_t* dst, size_t row_pitch, int flip_y) {
   if (!c) return RM_ERR_INVALID;
   if (!c->aa_dispatched)
-    return fail(c, RM_ERR_STATE, "rm_read_aa_mask: no rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine yet");
+    return fail(c, RM_ERR_STATE, "rm_read_aa_mask: no adaptive dispatch (rm_dispatch_adaptive* / rm_dispatch_refine*) yet");
   return read_image(c, c->d_aa_mask, 1, dst, row_pitch, flip_y);
 }
 
@@ -253,7 +336,7 @@ int rm_get_aa_mask(rm_ctx* c, void** device_ptr) {
 int rm_aa_refined(rm_ctx* c, int64_t* pixels) {
   if (!c || !pixels) return RM_ERR_INVALID;
   if (!c->aa_dispatched)
-    return fail(c, RM_ERR_STATE, "rm_aa_refined: no rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine yet");
+    return fail(c, RM_ERR_STATE, "rm_aa_refined: no adaptive dispatch (rm_dispatch_adaptive* / rm_dispatch_refine*) yet");
   const int rc = set_device(c);
   if (rc != RM_OK) return rc;
   unsigned long long n = 0;

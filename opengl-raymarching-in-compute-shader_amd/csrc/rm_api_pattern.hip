@@ -1,6 +1,8 @@
 // rm_api_pattern.hip — librm's C-ABI for sample-pattern frames (include/rm_api.h
-// RM_HAS_SAMPLE_PATTERN): rm_dispatch_pattern.  The pattern's
-// presets and its uv table are pure host math (rm_frame_math.hip).
+// RM_HAS_SAMPLE_PATTERN): rm_dispatch_pattern, and the pattern's
+// device table, which the pattern refinements of the adaptive calls share
+// (rm_api_adaptive.hip).  The pattern's presets and its uv table are pure host
+// math (rm_frame_math.hip).
 //
 // One such dispatch is, on the context's stream: the upload of the pattern's uv
 // table when the pattern differs from the last call's, and one kernel
@@ -35,19 +37,24 @@ bool same_pattern(const rm_sample_pattern& a, const rm_sample_pattern& b) {
          std::memcmp(a.dy, b.dy, sizeof(float) * (size_t)a.n) == 0;
 }
 
-// The device table of pattern p: the context's when p is the last call's, else
-// formed on the host (into pinned memory, once the previous upload has left it)
-// and uploaded on the context's stream, behind whatever still reads the old one.
-int ensure_table(rm_ctx* c, const rm_sample_pattern& p) {
+}  // namespace
+
+// The device table of pattern p: the context's when p is the last call's (of
+// rm_dispatch_pattern or of a pattern refinement, rm_api_adaptive.hip: they share
+// the table, its cache and pat_lo / pat_hi), else formed on the host (into pinned
+// memory, once the previous upload has left it) and uploaded on the context's
+// stream, behind whatever still reads the old one.
+int rm::ensure_table(rm_ctx* c, const rm_sample_pattern& p, const char* call) {
   if (c->pat.n != 0 && same_pattern(c->pat, p)) return RM_OK;
   const size_t bytes = table_cap(c) * sizeof(float);
-  int rc = ensure(c, c->pat_uv, bytes, "rm_dispatch_pattern: uv table");
+  const std::string what = std::string(call) + ": uv table";
+  int rc = ensure(c, c->pat_uv, bytes, what.c_str());
   if (rc != RM_OK) return rc;
   if (!c->pat_host) {
     if (hipHostMalloc(reinterpret_cast<void**>(&c->pat_host), bytes, hipHostMallocDefault) != hipSuccess) {
       c->pat_host = nullptr;
       (void)hipGetLastError();
-      return fail(c, RM_ERR_NOMEM, "rm_dispatch_pattern: host uv table of " + std::to_string(bytes) + " bytes");
+      return fail(c, RM_ERR_NOMEM, std::string(call) + ": host uv table of " + std::to_string(bytes) + " bytes");
     }
   }
   if (!c->pat_ev) RM_HIP(c, hipEventCreateWithFlags(&c->pat_ev, hipEventDisableTiming));
@@ -68,8 +75,6 @@ int ensure_table(rm_ctx* c, const rm_sample_pattern& p) {
   return RM_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int rm_dispatch_pattern(rm_ctx* c, const rm_sample_pattern* p) {
@@ -80,7 +85,7 @@ int rm_dispatch_pattern(rm_ctx* c, const rm_sample_pattern* p) {
   if ((rc = check_uniforms(c, c->u)) != RM_OK) return rc;
   if ((rc = set_device(c)) != RM_OK) return rc;
   if ((rc = order_after_batch(c)) != RM_OK) return rc;
-  if ((rc = ensure_table(c, *p)) != RM_OK) return rc;
+  if ((rc = ensure_table(c, *p, "rm_dispatch_pattern")) != RM_OK) return rc;
   rmd::Frame F = make_frame(c);
   // the 4x4 pixel tiles of the sample kernels, or for one sample the pixel kernels' 8x8
   // tiles, whatever u.AA says; the uniforms stay

@@ -56,4 +56,15 @@ struct BuiltinFast {
   }
 };
 
+// k_pixel's render of a primary ray (the projection bound of the miss exit too,
+// rm_kernels.hip march): what the one-sample pattern kernels render with
+// (rm_pattern.hip, rm_adaptive_pattern.hip).
+struct BuiltinPrimary {
+  const Frame& F;
+  __device__ __forceinline__ f3 render(f3 ro, f3 rd) const {
+    Cnt c = {0, 0, 0, 0, 0, 0};
+    return rmd::render<false, true>(F, ro, rd, c);
+  }
+};
+
 }  // namespace rmd

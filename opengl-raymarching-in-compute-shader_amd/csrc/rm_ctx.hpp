@@ -3,7 +3,7 @@
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
 // rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
 // rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling),
-// rm_api_pattern.hip (sample-pattern frames), rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
+// rm_api_pattern.hip (sample-pattern frames and the pattern's table), rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
 // families share: their frame constants, checks and staging buffers).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
@@ -74,6 +74,13 @@ hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& 
 // are pixel_grid's with aa set, at the pattern's device table P
 hipError_t launch_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
 hipError_t launch_table_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
+// pattern refinement in the adaptive calls (rm_adaptive_pattern.hip, rm_table_adaptive_pattern.hip):
+// the listed pixels rendered as the pattern frame's, at the pattern's device table P, on `waves`
+// one-wave workgroups
+hipError_t launch_adapt_refine_pattern(const rmd::Frame& F, const rmd::AdaptArgs& A, const rmd::PatternArgs& P,
+                                       int waves, hipStream_t s);
+hipError_t launch_table_adapt_refine_pattern(const rmd::Frame& F, const rmd::AdaptArgs& A, const rmd::PatternArgs& P,
+                                             int waves, hipStream_t s);
 // SDF mesh extraction (rm_mesh.hip), every dim >= 2: the waves' ballots and counts of M.vol,
 // their scans and the mesh's counts; then the vertices below M.vcap and the quads below
 // M.qcap; the device call's records below min(counts[0], vcap) out of n >= 1 staged ones
@@ -113,6 +120,7 @@ struct SceneKernels {
   decltype(launch_sdf_grid)* sdf_grid;
   decltype(launch_adapt_refine)* adapt_refine;
   decltype(launch_pattern)* pattern;
+  decltype(launch_adapt_refine_pattern)* adapt_refine_pattern;
 };
 
 // A device buffer the context owns and grows on demand (rm_api_query.hip ensure).
@@ -229,8 +237,9 @@ struct rm_ctx {
   // arrays (rm_mesh_args.hpp); rm_sdf_mesh's staging of the indices; rm_sdf_mesh_device's of
   // the records
   rm::DevBuf mesh_vol, mesh_waves, mesh_idx, mesh_attr;
-  // sample-pattern frames (rm_api_pattern.hip): the last pattern, its uv table on the device
-  // (uvx [width][n], then uvy [height][n]) and the range of its values per axis
+  // sample-pattern frames and pattern refinement (rm_api_pattern.hip ensure_table): the last
+  // pattern of either kind of call, its uv table on the device (uvx [width][n], then uvy
+  // [height][n]) and the range of its values per axis
   rm::DevBuf pat_uv;
   rm_sample_pattern pat{};  // pat.n == 0: none yet
   float pat_lo[2] = {0, 0}, pat_hi[2] = {0, 0};
@@ -371,6 +380,12 @@ int ensure(rm_ctx* c, DevBuf& b, size_t need, const char* what);
 // do not serve: multi-device, communicator, sharded, counting, graph-replay and (unless
 // gbuf_ok) G-buffer contexts.
 int refuse_extension(rm_ctx* c, const char* call, bool gbuf_ok = false);
+
+// ---- rm_api_pattern.hip -------------------------------------------------------------------
+// The device table of the valid pattern p (c->pat_uv, c->pat_lo / pat_hi): the context's when p
+// is the last call's, whichever of rm_dispatch_pattern and the pattern refinements made it, else
+// uploaded on the context's stream.  `call` starts the messages.
+int ensure_table(rm_ctx* c, const rm_sample_pattern& p, const char* call);
 
 // ---- rm_api_graph.hip: hipGraph replay -----------------------------------------------------
 void graph_release(rm_ctx* c);

@@ -42,15 +42,6 @@ __global__ __launch_bounds__(64, 8) void k_pattern(PatternFrame B, PatternArgs P
   }
 }
 
-// k_pixel's render of a primary ray (the projection bound of the miss exit too, rm_kernels.hip march).
-struct BuiltinPrimary {
-  const Frame& F;
-  __device__ __forceinline__ f3 render(f3 ro, f3 rd) const {
-    Cnt c = {0, 0, 0, 0, 0, 0};
-    return rmd::render<false, true>(F, ro, rd, c);
-  }
-};
-
 // A pattern of one sample (temporal jitter): k_pixel's wave, an 8x8 pixel tile, with
 // the uv from the pattern's table.
 __global__ __launch_bounds__(64, 8) void k_pattern_one(Frame F, PatternArgs P) {

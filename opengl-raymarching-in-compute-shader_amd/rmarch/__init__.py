@@ -57,6 +57,7 @@ RM_PATTERN_GRID2 = 1       # n 4, {-.25, +.25}^2, x fastest
 RM_PATTERN_RGSS = 2        # n 4, rotated grid
 RM_PATTERN_GRID3 = 3       # n 9, {-.34375, 0, +.34375}^2, x fastest
 RM_PATTERN_GRID4 = 4       # n 16, {-.375, -.125, +.125, +.375}^2, x fastest
+RM_HAS_ADAPTIVE_PATTERN = 1  # Renderer.dispatch_adaptive_pattern / dispatch_refine_pattern
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -345,6 +346,9 @@ _SIGS = {
     "rm_sample_pattern_init": (C.c_int, [C.POINTER(rm_sample_pattern), C.c_int32]),
     "rm_pattern_uv_table": (C.c_int, [C.POINTER(rm_sample_pattern), C.c_int32, C.c_int32, _P, _P]),
     "rm_dispatch_pattern": (C.c_int, [_P, C.POINTER(rm_sample_pattern)]),
+    "rm_dispatch_adaptive_pattern": (C.c_int, [_P, C.POINTER(rm_aa_criteria), C.POINTER(rm_sample_pattern)]),
+    "rm_dispatch_refine_pattern": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(rm_sample_pattern)]),
+    "rm_dispatch_refine_pattern_device": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(rm_sample_pattern)]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -763,6 +767,46 @@ class Renderer:
             self.set_uniforms(u)
         p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
         _check(lib().rm_dispatch_pattern(self._h, C.byref(p)), self._h)
+
+    # -- pattern refinement (rm_dispatch_adaptive_pattern, rm_dispatch_refine_pattern)
+    def dispatch_adaptive_pattern(self, u: Optional[rm_uniforms] = None, criteria=None,
+                                  pattern=RM_PATTERN_GRID4) -> None:
+        """dispatch_adaptive_edges with a pattern's samples on the flagged pixels
+        (rm_dispatch_adaptive_pattern): the AA-off frame with every flagged pixel replaced by
+        dispatch_pattern's.  `criteria` is an rm_aa_criteria, a dict of dispatch_adaptive_edges'
+        keywords, or None for rm_aa_criteria_init's defaults; `pattern` as in dispatch_pattern.
+        Asynchronous; reads back like dispatch_adaptive_edges()."""
+        if u is not None:
+            self.set_uniforms(u)
+        if isinstance(criteria, rm_aa_criteria):
+            cr = criteria
+        else:
+            cr = rm_aa_criteria()
+            _check(lib().rm_aa_criteria_init(C.byref(cr)))
+            for k, v in (criteria or {}).items():
+                if k not in ("edges", "color_threshold", "depth_rel", "normal_cos"):
+                    raise ValueError(f"dispatch_adaptive_pattern: unknown criterion {k!r}")
+                setattr(cr, k, v)
+        p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
+        _check(lib().rm_dispatch_adaptive_pattern(self._h, C.byref(cr), C.byref(p)), self._h)
+
+    def dispatch_refine_pattern(self, mask, pattern=RM_PATTERN_GRID4, u: Optional[rm_uniforms] = None,
+                                row_pitch: int = 0) -> None:
+        """dispatch_refine with a pattern's samples on the flagged pixels
+        (rm_dispatch_refine_pattern / _device): `mask` as in dispatch_refine, `pattern` as in
+        dispatch_pattern.  G-buffer contexts are served: pass 1 writes the records."""
+        if u is not None:
+            self.set_uniforms(u)
+        p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
+        if isinstance(mask, np.ndarray):
+            m = mask if mask.dtype == np.uint8 else (mask != 0).astype(np.uint8)
+            if m.ndim != 2 or m.shape != (self.height, self.width):
+                raise ValueError("dispatch_refine_pattern: mask must be (height, width)")
+            if m.strides[1] != 1 or m.strides[0] < self.width:
+                m = np.ascontiguousarray(m)
+            _check(lib().rm_dispatch_refine_pattern(self._h, m.ctypes.data, m.strides[0], C.byref(p)), self._h)
+        else:
+            _check(lib().rm_dispatch_refine_pattern_device(self._h, mask, int(row_pitch), C.byref(p)), self._h)
 
     def read_frame_rgba8(self, k: int, flip_y: bool = False) -> np.ndarray:
         out = np.empty((self.rows, self.width, 4), np.uint8)

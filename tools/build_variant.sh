@@ -49,10 +49,10 @@ case "$*" in
 esac
 # the ray-query, G-buffer, SDF-query, adaptive and mesh kernels, as the Makefile builds them
 # (absent in older revisions)
-for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges rm_mesh rm_pattern; do
+for f in rm_trace rm_gbuffer rm_sdf rm_adaptive rm_adaptive_edges rm_mesh rm_pattern rm_adaptive_pattern; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
-for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern; do
+for f in rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern rm_table_adaptive_pattern; do
   [ -f "$src/$pkg/csrc/$f.hip" ] && { /opt/rocm/bin/hipcc $flags -fno-slp-vectorize -mllvm -amdgpu-inline-max-bb=8000 -c "$src/$pkg/csrc/$f.hip" -o "$b/$f.o" & }
 done
 /opt/rocm/bin/hipcc $flags -x c++ -c "$src/$pkg/csrc/rm_host.cpp" -o "$b/rm_host.o" &
