@@ -113,11 +113,6 @@ __global__ __launch_bounds__(kAdaptScanLanes) void k_adapt_scan(const uint8_t* _
   if (t == 0) *total = base;
 }
 
-// Lanes of the wave below this one that are set in m (v_mbcnt).
-__device__ __forceinline__ uint32_t adapt_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 __global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_scatter(AdaptArgs A) {
   int px, py;
   const bool in = adapt_pixel(A, px, py);
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(64 * kAdaptWaves) void k_adapt_scatter(AdaptArgs A)
   const unsigned long long m = __ballot(flag);
   if (!flag) return;
   // (a flagged lane is inside the frame: its wave's tile is a real one)
-  const size_t at = (size_t)A.offsets[(size_t)blockIdx.y * (size_t)A.tiles_x + adapt_tx()] + adapt_prefix(m);
+  const size_t at = (size_t)A.offsets[(size_t)blockIdx.y * (size_t)A.tiles_x + adapt_tx()] + lane_rank(m);
   A.list[at] = (uint32_t)px | ((uint32_t)py << 16);  // both <= 65535
 }
 
@@ -169,15 +164,13 @@ __global__ __launch_bounds__(64, 8) void k_adapt_refine(AdaptFrame B, AdaptArgs 
         col = render<false>(F, ro, rd, c);
       }
     }
-    const int ol = adapt_lane();
-    const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
-    const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
-    const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+    const int ol = out_lane();
+    const Quad nb = quad_neighbours(col, ol);
     if ((ol & 3) == 0 && (ol >> 2) < n) {
       const uint32_t e = ent[ol >> 2];
       const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
-      const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3, o2 = ((col.z + b1) + b2) + b3;
-      store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+      const f3 o = quad_sum(col, nb);
+      store_pixel(F, idx, o.x / 4.0f, o.y / 4.0f, o.z / 4.0f, 1.0f);
     }
   }
 }

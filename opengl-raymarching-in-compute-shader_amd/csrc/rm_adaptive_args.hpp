@@ -2,7 +2,7 @@
 // (rm_dispatch_adaptive / rm_dispatch_adaptive_edges / rm_dispatch_refine, DESIGN.md
 // §4.12), shared by the kernels (rm_adaptive.hip, rm_adaptive_edges.hip,
 // rm_table_adaptive.hip) and the host (rm_api_adaptive.hip), the refine kernels'
-// lane helper (adapt_lane) and their round over Fast (adapt_refine_round).
+// round over Fast (adapt_refine_round).
 #pragma once
 
 #include <cstddef>
@@ -40,14 +40,6 @@ struct EdgeArgs {
   float depth_rel, normal_cos;
 };
 
-// The lane id re-formed after the march (rm_table.hip out_lane): the list entry is
-// read again from it instead of px, py staying live across the render.
-__device__ __forceinline__ int adapt_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
 // One round of a refine kernel: group g of 16 list entries x 4 samples on one
 // wave, over the fast-path scene sc (Fast, rm_trace.hpp): cast_ray, render, the
 // three-shuffle sum and store_pixel of the AA kernels' sample bodies in the same
@@ -73,15 +65,14 @@ __device__ __forceinline__ void adapt_refine_round(const Frame& F, const AdaptAr
       col = sc.render(ro, rd);
     }
   }
-  const int ol = adapt_lane();
-  const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
-  const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
-  const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+  const int ol = out_lane();
+  // (the list entry is read again from the re-formed lane id: px, py do not stay live across the render)
+  const Quad nb = quad_neighbours(col, ol);
   if ((ol & 3) == 0 && (ol >> 2) < n) {
     const uint32_t e = ent[ol >> 2];
     const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
-    const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3, o2 = ((col.z + b1) + b2) + b3;
-    store_pixel(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+    const f3 o = quad_sum(col, nb);
+    store_pixel(F, idx, o.x / 4.0f, o.y / 4.0f, o.z / 4.0f, 1.0f);
   }
 }
 

@@ -37,7 +37,7 @@ __device__ __forceinline__ void adapt_pattern_round(const Frame& F, const AdaptA
     // the lane id formed here too, not from threadIdx.x: what the compiler derives from
     // that (the entry's number, its address in the group, the sample lane) is invariant
     // in one or both loops and was kept live across the render, 8 VGPRs spilled
-    const int lane = adapt_lane();
+    const int lane = out_lane();
     const int s = 4 * r + (lane & 3);
     if ((lane >> 2) < ne && s < P.n) {
       const uint32_t e = ent[lane >> 2];
@@ -48,43 +48,14 @@ __device__ __forceinline__ void adapt_pattern_round(const Frame& F, const AdaptA
     }
   }
   // the lane id re-formed, as the refinement does: nothing of the entry stays live across the render
-  const int ol = adapt_lane();
-  const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
-  const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
-  const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+  const int ol = out_lane();
+  const Quad nb = quad_neighbours(col, ol);
   const int q = ol >> 2;
   if ((ol & 3) != 0 || q >= ne) return;
-  float a0 = col.x, a1 = col.y, a2 = col.z;
-  if (r > 0) {
-    a0 = acc[q] + col.x;
-    a1 = acc[16 + q] + col.y;
-    a2 = acc[32 + q] + col.z;
-  }
-  const int left = P.n - 4 * r;  // the pattern's samples from this round on (uniform), >= 1
-  if (left > 1) {
-    a0 += r1;
-    a1 += g1;
-    a2 += b1;
-  }
-  if (left > 2) {
-    a0 += r2;
-    a1 += g2;
-    a2 += b2;
-  }
-  if (left > 3) {
-    a0 += r3;
-    a1 += g3;
-    a2 += b3;
-  }
-  if (left > 4) {
-    acc[q] = a0;
-    acc[16 + q] = a1;
-    acc[32 + q] = a2;
-  } else {
+  pattern_accumulate(F, P, r, q, col, nb, acc, [&] {
     const uint32_t e = ent[q];
-    const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
-    store_pixel(F, idx, a0 / P.nf, a1 / P.nf, a2 / P.nf, 1.0f);
-  }
+    return (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);
+  });
 }
 
 // A pattern of one sample: group g of 64 list entries, one lane per entry, so no lane
@@ -107,7 +78,7 @@ __device__ __forceinline__ void adapt_pattern_pixel(const Frame& F, const AdaptA
       col = sc.render(ro, rd);
     }
   }
-  const int ol = adapt_lane();
+  const int ol = out_lane();
   if (ol >= ne) return;
   const uint32_t e = ent[ol];
   const size_t idx = (size_t)(e >> 16) * (size_t)F.width + (size_t)(e & 0xffffu);

@@ -46,18 +46,6 @@ __device__ unsigned long long* g_wave_times;
 template <bool COUNT>
 constexpr bool kLean = RM_LEAN_FIXED_WORK != 0 && !COUNT;
 
-struct Cnt {
-  uint32_t rays, march, reflect, shadow, normals, lights;
-};
-
-// Keeps the compiler from hoisting a value (and its registers) across a loop,
-// and feeds the RM_DBL_<PHASE> cost probes an opaque copy of their inputs.
-__device__ __forceinline__ float opaque(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ f3 opaque(f3 v) { return mk(opaque(v.x), opaque(v.y), opaque(v.z)); }
-
 // RayMarch glsl:125-142 / reflectedRay glsl:144-161.  Returns t or -1.
 // UNIT: a primary ray of a frame whose rays all have |rd| within 2^-20 of 1
 // (Frame::unit_rd, checked on the host): |rd| = 1 serves every bound that
@@ -596,12 +584,7 @@ __device__ __forceinline__ void pixel_body(const Frame& F, int rowslot, float4* 
   store_pixel<kLean<COUNT>>(F, idx, o0, o1, o2, o3);
   if (COUNT) {
     F.sdf_counts[idx] = c.march + c.reflect + c.shadow + 4u * c.normals;
-    atomicAdd(&F.counters[0], (unsigned long long)c.rays);
-    atomicAdd(&F.counters[1], (unsigned long long)c.march);
-    atomicAdd(&F.counters[2], (unsigned long long)c.reflect);
-    atomicAdd(&F.counters[3], (unsigned long long)c.shadow);
-    atomicAdd(&F.counters[4], (unsigned long long)c.normals);
-    atomicAdd(&F.counters[5], (unsigned long long)c.lights);
+    flush_counts(F, c);
   }
 }
 
@@ -642,30 +625,12 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot, float4*
     if constexpr (GBUF) col = render<COUNT, false>(F, ro, rd, c, GbufStore{gbuf + 2 * idx, s == 0});
     else col = render<COUNT>(F, ro, rd, c);
   }
-#ifdef RM_DPP_AA
-  // the quad's other samples by DPP quad permutes (lane s = 0 reads lanes 1, 2, 3
-  // of its quad): VALU moves instead of LDS permutes
-  auto q1 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x39, 0xf, 0xf, false)); };
-  auto q2 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false)); };
-  auto q3 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x93, 0xf, 0xf, false)); };
-  const float r1 = q1(col.x), g1 = q1(col.y), b1 = q1(col.z);
-  const float r2 = q2(col.x), g2 = q2(col.y), b2 = q2(col.z);
-  const float r3 = q3(col.x), g3 = q3(col.y), b3 = q3(col.z);
-#else
-  const float r1 = __shfl(col.x, lane + 1), g1 = __shfl(col.y, lane + 1), b1 = __shfl(col.z, lane + 1);
-  const float r2 = __shfl(col.x, lane + 2), g2 = __shfl(col.y, lane + 2), b2 = __shfl(col.z, lane + 2);
-  const float r3 = __shfl(col.x, lane + 3), g3 = __shfl(col.y, lane + 3), b3 = __shfl(col.z, lane + 3);
-#endif
+  const Quad nb = quad_neighbours(col, lane);
   uint32_t cnt = 0;
   if (COUNT) {
     const uint32_t mine = c.march + c.reflect + c.shadow + 4u * c.normals;
     cnt = mine + __shfl(mine, lane + 1) + __shfl(mine, lane + 2) + __shfl(mine, lane + 3);
-    atomicAdd(&F.counters[0], (unsigned long long)c.rays);
-    atomicAdd(&F.counters[1], (unsigned long long)c.march);
-    atomicAdd(&F.counters[2], (unsigned long long)c.reflect);
-    atomicAdd(&F.counters[3], (unsigned long long)c.shadow);
-    atomicAdd(&F.counters[4], (unsigned long long)c.normals);
-    atomicAdd(&F.counters[5], (unsigned long long)c.lights);
+    flush_counts(F, c);
   }
 #ifdef RM_WAVE_TIMES
   // diagnostic (tools/wave_timeline.hip): per-wave start/end and hardware slot
@@ -680,18 +645,16 @@ __device__ __forceinline__ void sample_body(const Frame& F, int rowslot, float4*
 #endif
   if (s != 0) return;
   if (py >= 0) {
-    const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3,
-                o2 = ((col.z + b1) + b2) + b3;
+    const f3 o = quad_sum(col, nb);
 #ifdef RM_DBL_STORE
     // cost probe: the AA sum, quantise and pack a second time (store_pixel packs twice)
     if (!COUNT) {
-      const float p0 = ((opaque(col.x) + r1) + r2) + r3, p1 = ((opaque(col.y) + g1) + g2) + g3,
-                  p2 = ((opaque(col.z) + b1) + b2) + b3;
-      store_pixel<kLean<COUNT>>(F, idx, vmin(o0 / 4.0f, p0 / 4.0f), vmin(o1 / 4.0f, p1 / 4.0f), vmin(o2 / 4.0f, p2 / 4.0f), 1.0f);
+      const f3 p = quad_sum(opaque(col), nb);
+      store_pixel<kLean<COUNT>>(F, idx, vmin(o.x / 4.0f, p.x / 4.0f), vmin(o.y / 4.0f, p.y / 4.0f), vmin(o.z / 4.0f, p.z / 4.0f), 1.0f);
       return;
     }
 #endif
-    store_pixel<kLean<COUNT>>(F, idx, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+    store_pixel<kLean<COUNT>>(F, idx, o.x / 4.0f, o.y / 4.0f, o.z / 4.0f, 1.0f);
   } else {
     store_pixel<kLean<COUNT>>(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
     if (GBUF) gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
@@ -719,20 +682,8 @@ __global__ __launch_bounds__(64, 8) void k_sample(Frame F) {
 }
 #endif
 
-// Frame batches (rm_dispatch_frames): n frames in one grid of gridDim.y x n tile
-// rows.  The hardware dispatches workgroups in x, y, z order; (y, z) is read
-// row-major over the frames: dispatch slot L = z gridDim.y + y renders tile-row
-// slot L / n (inside-out order, tile_row) of frame L % n, so the slowest rows of
-// every frame of the batch start first and the launch ends on the cheap rows of
-// all its frames (round 5; frame-major order ended each launch on its last
-// frame's cheap rows but started every frame's slow rows only after the previous
-// frame's whole grid).  Production builds only.
-__device__ __forceinline__ void batch_slot(int& frame, int& rowslot) {
-  const int L = blockIdx.z * gridDim.y + blockIdx.y, n = gridDim.z;
-  // uniform: kept in SGPRs (the division is VALU code)
-  rowslot = __builtin_amdgcn_readfirstlane(L / n);
-  frame = __builtin_amdgcn_readfirstlane(L - rowslot * n);
-}
+// Frame batches (rm_dispatch_frames): the workgroup's frame and tile-row slot by
+// batch_slot (rm_scene.hpp).  Production builds only.
 #ifndef RM_KERNELS_AA_ONLY
 __global__ __launch_bounds__(64, 8) void k_pixel_frames(FrameBatch B) {
   int f, r;

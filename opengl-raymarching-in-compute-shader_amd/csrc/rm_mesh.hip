@@ -29,13 +29,9 @@
 #include <hip/hip_runtime.h>
 
 #include "rm_mesh_args.hpp"
+#include "rm_scene.hpp"  // lane_rank
 
 namespace rmd {
-
-// Lanes of the wave below this one that are set in m (v_mbcnt).
-__device__ __forceinline__ uint32_t mesh_prefix(unsigned long long m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 // Grid coordinate idx of one axis, as rm_sdf.hpp sdf_grid_coord: one IEEE
 // multiply, then one IEEE add.
@@ -275,7 +271,7 @@ __device__ __forceinline__ void mesh_task_vertices(const MeshArgs& M, uint32_t b
   const unsigned long long m = M.active[b];
   const long long v0 = (long long)(M.chunks[(size_t)(b >> kMeshScanShift) * 2] + M.voff[b]);
   if (v0 >= M.vcap) return;
-  const long long v = v0 + (long long)mesh_prefix(m);
+  const long long v = v0 + (long long)lane_rank(m);
   if (!((m >> (threadIdx.x & 63u)) & 1ull) || v >= M.vcap) return;
   uint32_t row;
   int ix, iy, iz;
@@ -358,7 +354,7 @@ __device__ __forceinline__ void mesh_task_quads(const MeshArgs& M, uint32_t b) {
   const bool ex = (bx >> lane) & 1ull, ey = (by >> lane) & 1ull, ez = (bz >> lane) & 1ull, a_in = (bi >> lane) & 1ull;
   if (!(ex || ey || ez)) return;
   // the quads of the lanes below come first, then the lane's own in axis order
-  unsigned long long q = q0 + (unsigned long long)(mesh_prefix(bx) + mesh_prefix(by) + mesh_prefix(bz));
+  unsigned long long q = q0 + (unsigned long long)(lane_rank(bx) + lane_rank(by) + lane_rank(bz));
   uint32_t row;
   int i, j, k;
   (void)mesh_point(M, b, row, i, j, k);

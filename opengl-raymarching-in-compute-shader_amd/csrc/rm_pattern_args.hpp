@@ -1,7 +1,7 @@
 // rm_pattern_args.hpp — the kernel arguments of a sample-pattern frame
 // (rm_dispatch_pattern, include/rm_api.h RM_HAS_SAMPLE_PATTERN),
 // shared by the kernels (rm_pattern.hip, rm_table_pattern.hip) and the host
-// (rm_api_pattern.hip), and the kernels' round over Fast (pattern_round).
+// (rm_api_pattern.hip), the kernels' round over Fast (pattern_round) and a round's tail (pattern_accumulate).
 #pragma once
 
 #include <cstddef>
@@ -23,6 +23,44 @@ struct PatternArgs {
 // [channel][pixel].  Registers would have to stay live across the render, which
 // has none to spare at 8 waves per SIMD.
 constexpr int kPatternAcc = 3 * 16;
+
+// The tail of a round for lane s == 0 of pixel q of the wave's 16: the round's samples
+// added onto the pixel's running sum in sample order, samples past n taking no part;
+// a round that is not the last keeps the sum in acc, the last divides by n and stores
+// at idx() (a functor: the index is formed, a list entry re-read, on the store path only).
+template <class Idx>
+__device__ __forceinline__ void pattern_accumulate(const Frame& F, const PatternArgs& P, int r, int q, f3 col,
+                                                   const Quad& nb, float* acc, const Idx& idx) {
+  float a0 = col.x, a1 = col.y, a2 = col.z;
+  if (r > 0) {
+    a0 = acc[q] + col.x;
+    a1 = acc[16 + q] + col.y;
+    a2 = acc[32 + q] + col.z;
+  }
+  const int left = P.n - 4 * r;  // the pattern's samples from this round on (uniform), >= 1
+  if (left > 1) {
+    a0 += nb.c1.x;
+    a1 += nb.c1.y;
+    a2 += nb.c1.z;
+  }
+  if (left > 2) {
+    a0 += nb.c2.x;
+    a1 += nb.c2.y;
+    a2 += nb.c2.z;
+  }
+  if (left > 3) {
+    a0 += nb.c3.x;
+    a1 += nb.c3.y;
+    a2 += nb.c3.z;
+  }
+  if (left > 4) {
+    acc[q] = a0;
+    acc[16 + q] = a1;
+    acc[32 + q] = a2;
+  } else {
+    store_pixel(F, idx(), a0 / P.nf, a1 / P.nf, a2 / P.nf, 1.0f);
+  }
+}
 
 // Round r of a pattern frame's wave: the 4x4 pixel tile (bx, by) x 4 sample lanes of
 // the AA kernels' sample bodies, lane l on pixel l >> 2 and sample 4 r + (l & 3) of
@@ -46,43 +84,13 @@ __device__ __forceinline__ void pattern_round(const Frame& F, const PatternArgs&
     }
   }
   // the lane id re-formed, as the refinement does: nothing of the pixel stays live across the render
-  const int ol = adapt_lane();
-  const float r1 = __shfl(col.x, ol + 1), g1 = __shfl(col.y, ol + 1), b1 = __shfl(col.z, ol + 1);
-  const float r2 = __shfl(col.x, ol + 2), g2 = __shfl(col.y, ol + 2), b2 = __shfl(col.z, ol + 2);
-  const float r3 = __shfl(col.x, ol + 3), g3 = __shfl(col.y, ol + 3), b3 = __shfl(col.z, ol + 3);
+  const int ol = out_lane();
+  const Quad nb = quad_neighbours(col, ol);
   const int q = ol >> 2;
   const int px = bx * 4 + (q & 3), py = by * 4 + (q >> 2);
   if ((ol & 3) != 0 || px >= F.width || py >= F.rows) return;
-  float a0 = col.x, a1 = col.y, a2 = col.z;
-  if (r > 0) {
-    a0 = acc[q] + col.x;
-    a1 = acc[16 + q] + col.y;
-    a2 = acc[32 + q] + col.z;
-  }
-  const int left = P.n - 4 * r;  // the pattern's samples from this round on (uniform), >= 1
-  if (left > 1) {
-    a0 += r1;
-    a1 += g1;
-    a2 += b1;
-  }
-  if (left > 2) {
-    a0 += r2;
-    a1 += g2;
-    a2 += b2;
-  }
-  if (left > 3) {
-    a0 += r3;
-    a1 += g3;
-    a2 += b3;
-  }
-  if (left > 4) {
-    acc[q] = a0;
-    acc[16 + q] = a1;
-    acc[32 + q] = a2;
-  } else {
-    const size_t idx = (size_t)py * (size_t)F.width + (size_t)px;
-    store_pixel(F, idx, a0 / P.nf, a1 / P.nf, a2 / P.nf, 1.0f);
-  }
+  // (px, py captured by value: by reference k_pattern's code changed in size)
+  pattern_accumulate(F, P, r, q, col, nb, acc, [&, px, py] { return (size_t)py * (size_t)F.width + (size_t)px; });
 }
 
 // A pattern of one sample: the frame kernels' pixel tile instead, one lane per pixel
@@ -100,7 +108,7 @@ __device__ __forceinline__ void pattern_pixel(const Frame& F, const PatternArgs&
     cast_ray(F, P.uvx[px], P.uvy[py], ro, rd);
     col = sc.render(ro, rd);
   }
-  const int ol = adapt_lane();
+  const int ol = out_lane();
   const size_t idx = (size_t)(by * 8 + (ol >> 3)) * (size_t)F.width + (size_t)(bx * 8 + (ol & 7));
   store_pixel(F, idx, col.x, col.y, col.z, 1.0f);
 }

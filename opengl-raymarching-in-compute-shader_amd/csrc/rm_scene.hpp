@@ -11,6 +11,9 @@
 //     (glsl:105, ties go to the later primitive) with a compare + select;
 //   * sdPlane(p, (0,1,0,5.5)) = dot(p,(0,1,0)) + 5.5 is computed as p.y + 5.5
 //     (the x*0 and z*0 terms are signed zeros that cannot change the sum).
+// Also here, once for the built-in and the table kernels and every family around them
+// (after store_pixel): the work counters (Cnt, flush_counts), opaque, out_lane,
+// lane_rank, batch_slot and the four sample lanes' sum (quad_neighbours, quad_sum).
 #pragma once
 
 #ifndef __HIPCC_RTC__
@@ -1157,6 +1160,89 @@ __device__ __forceinline__ void store_pixel(const Frame& F, size_t idx, float r,
     }
   }
   if (F.rgba32f) reinterpret_cast<float4*>(F.rgba32f)[idx] = make_float4(r, g, b, a);
+}
+
+// ---- what every kernel family does around its render, written once ------------------
+// A lane's work counters (the counting builds), added to the frame's once per lane.
+struct Cnt {
+  uint32_t rays, march, reflect, shadow, normals, lights;
+};
+__device__ __forceinline__ void flush_counts(const Frame& F, const Cnt& c) {
+  atomicAdd(&F.counters[0], (unsigned long long)c.rays);
+  atomicAdd(&F.counters[1], (unsigned long long)c.march);
+  atomicAdd(&F.counters[2], (unsigned long long)c.reflect);
+  atomicAdd(&F.counters[3], (unsigned long long)c.shadow);
+  atomicAdd(&F.counters[4], (unsigned long long)c.normals);
+  atomicAdd(&F.counters[5], (unsigned long long)c.lights);
+}
+
+// An opaque VGPR copy.  It keeps the compiler from hoisting a value (and its
+// registers) across a loop; it puts a uniform value into a VGPR (an f32 op with an
+// SGPR operand takes a whole VALU issue slot, with VGPRs two pair in one, DESIGN.md
+// §6); and it feeds the RM_DBL_<PHASE> / RM_TDBL_<PHASE> cost probes their inputs
+// (diagnostic builds, tools/ab_kernel.py: a phase run twice, its marginal cost per
+// frame).
+__device__ __forceinline__ float opaque(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ f3 opaque(f3 v) { return mk(opaque(v.x), opaque(v.y), opaque(v.z)); }
+
+// The lane id re-formed after the render (v_mbcnt, one-wave workgroups: the same
+// value as threadIdx.x): the output pixel's coordinates and index, or its list
+// entry, come from it instead of staying live across the render, where both table
+// kernels spilled them to scratch (5 VGPRs, round 5).  Volatile so that LLVM cannot
+// fold it back onto the prologue's threadIdx.x.
+__device__ __forceinline__ int out_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+// Lanes of the wave below this one that are set in m (v_mbcnt).
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// Frame batches (rm_dispatch_frames): n frames in one grid of gridDim.y x n tile
+// rows.  The hardware dispatches workgroups in x, y, z order; (y, z) is read
+// row-major over the frames: dispatch slot L = z gridDim.y + y renders tile-row
+// slot L / n (inside-out order, tile_row) of frame L % n, so the slowest rows of
+// every frame of the batch start first and the launch ends on the cheap rows of
+// all its frames (round 5; frame-major order ended each launch on its last
+// frame's cheap rows but started every frame's slow rows only after the previous
+// frame's whole grid).  Production builds only.
+__device__ __forceinline__ void batch_slot(int& frame, int& rowslot) {
+  const int L = blockIdx.z * gridDim.y + blockIdx.y, n = gridDim.z;
+  // uniform: kept in SGPRs (the division is VALU code)
+  rowslot = __builtin_amdgcn_readfirstlane(L / n);
+  frame = __builtin_amdgcn_readfirstlane(L - rowslot * n);
+}
+
+// The four sample lanes of a pixel sit in adjacent lanes s = lane & 3.  Lane s = 0
+// takes the colours of lanes 1, 2, 3 (every lane of the wave makes the calls) and sums
+// in the reference's fixed order ((c0 + c1) + c2) + c3 (glsl:315-335).
+struct Quad {
+  f3 c1, c2, c3;
+};
+__device__ __forceinline__ Quad quad_neighbours(f3 col, int lane) {
+#ifdef RM_DPP_AA
+  // the quad's other samples by DPP quad permutes (lane s = 0 reads lanes 1, 2, 3
+  // of its quad): VALU moves instead of LDS permutes
+  auto q1 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x39, 0xf, 0xf, false)); };
+  auto q2 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false)); };
+  auto q3 = [](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x93, 0xf, 0xf, false)); };
+  return Quad{mk(q1(col.x), q1(col.y), q1(col.z)), mk(q2(col.x), q2(col.y), q2(col.z)),
+              mk(q3(col.x), q3(col.y), q3(col.z))};
+#else
+  const float r1 = __shfl(col.x, lane + 1), g1 = __shfl(col.y, lane + 1), b1 = __shfl(col.z, lane + 1);
+  const float r2 = __shfl(col.x, lane + 2), g2 = __shfl(col.y, lane + 2), b2 = __shfl(col.z, lane + 2);
+  const float r3 = __shfl(col.x, lane + 3), g3 = __shfl(col.y, lane + 3), b3 = __shfl(col.z, lane + 3);
+  return Quad{mk(r1, g1, b1), mk(r2, g2, b2), mk(r3, g3, b3)};
+#endif
+}
+__device__ __forceinline__ f3 quad_sum(f3 col, const Quad& n) {
+  return mk(((col.x + n.c1.x) + n.c2.x) + n.c3.x, ((col.y + n.c1.y) + n.c2.y) + n.c3.y,
+            ((col.z + n.c1.z) + n.c2.z) + n.c3.z);
 }
 
 // ---- the primary hit's way out of render / trender (RM_OUT_GBUFFER) ----

@@ -56,9 +56,6 @@
 
 namespace rmd {
 
-struct TCnt {
-  uint32_t rays, march, reflect, shadow, normals, lights;
-};
 // compile-time flags of the march-loop variants (no <type_traits> under hiprtc)
 struct Yes { static constexpr bool value = true; };
 struct No { static constexpr bool value = false; };
@@ -630,16 +627,6 @@ struct TLazy {
   }
 };
 
-// An opaque VGPR copy: a uniform value used as a VGPR operand (an f32 op with an
-// SGPR operand takes a whole VALU issue slot, with VGPRs two pair in one,
-// DESIGN.md §6), and the RM_TDBL_<PHASE> probes' opaque inputs (diagnostic
-// builds, tools/ab_kernel.py: a phase run twice, its marginal cost per frame).
-__device__ __forceinline__ float topaque(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ f3 topaque(f3 v) { return mk(topaque(v.x), topaque(v.y), topaque(v.z)); }
-
 struct THit {
   float t;  // -1: the dummy RayHit {-1, 0, -1, 1.0} (glsl:128)
   int id;
@@ -647,6 +634,7 @@ struct THit {
   f3 color;
   float d;  // a hit's last distance: sdf at the hit point itself (GetNormal's centre sample)
 };
+__device__ __forceinline__ THit tmiss() { return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f}; }
 
 // ---- the built-in kernel's march shape for reference-shaped tables -------------
 // A table whose bounded entries all sit in lazy slots and whose one plane is its
@@ -696,13 +684,6 @@ __device__ __forceinline__ bool glazy_table(const Table& S) {
 //     TLazy's own budget, at rate inv, serves the host's step-0 gaps.
 //   * the exact evaluations of a step run inline in table order against the
 //     running minimum m (the plane first: it is the last entry and wins ties).
-template <int KL>
-struct SLazy {
-  float te[KL];
-  float temin, s0, s1, inv, invp;
-  int idb;  // the entry the last block's values made the winner (the plane: n - 1)
-};
-
 // The minimum over the expiries, three at a time (v_min3_f32): the first ns
 // (a compile-time count) in a specialised kernel; all KL in the generic one,
 // whose unused slots hold +inf (a runtime bound would index the array, which
@@ -721,9 +702,72 @@ __device__ __forceinline__ float slot_min(const float (&te)[KL], int ns) {
   return m;
 }
 
+// The expiries of smarch and gmarch (below): the set-up, the seeding and a slot's
+// re-test are the same in both.
+template <int KL>
+struct SLazy {
+  float te[KL];
+  float temin, s0, s1, inv, invp;
+  int idb;  // the entry the last block's values made the winner (the plane: n - 1)
+
+  // The slack's line and the two rates.  smax(): the largest slope of a plane's value
+  // along the ray (its float error is far inside the 2^-8 added to s1).
+  template <class Smax>
+  __device__ __forceinline__ void rates(const float* ex, f3 ro, f3 rd, const Smax& smax) {
+    const float sig2 = 2.0f * ex[rm::EX_SIGMA];
+    const float rdl = __builtin_amdgcn_sqrtf(dot(rd, rd)) * (1.0f + 0x1p-16f);  // >= |rd|
+    const float rd1 = ((fabsf(rd.x) + fabsf(rd.y)) + fabsf(rd.z)) * (1.0f + 0x1p-16f);
+    const float ro1 = (fabsf(ro.x) + fabsf(ro.y)) + fabsf(ro.z);
+    s0 = sig2 * (2.0f * ro1 + ex[rm::EX_S]) * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
+    s1 = sig2 * rd1 * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
+    inv = (1.0f - 0x1p-10f) *
+          __builtin_amdgcn_rcpf((1.0f + ex[rm::EX_LIP]) * rdl + sig2 * rd1) * (1.0f - 0x1p-16f);
+    const float ratep = (rdl + smax()) + s1 * (1.0f + 0x1p-8f);
+    invp = ratep > 0.0f ? (1.0f - 0x1p-10f) * __builtin_amdgcn_rcpf(ratep) * (1.0f - 0x1p-16f) : 0.0f;
+  }
+
+  // Where the march starts: t and the last distance dl, the sdf evaluations i0 the
+  // first loop step brings the count to, and the slots' first expiries.  With the
+  // host's step 0 at the camera (tmarch below; table_prep_host: slot j's gap with U =
+  // the planes at the camera) the gaps are TLazy's, their expiries at TLazy's rate.
+  // False: the start is past the provable miss T.
+  __device__ __forceinline__ bool seed(const float* prep, int ns, float T, float& t, float& dl, int& i0) {
+    t = 0.0f, dl = 0.0f;
+    i0 = 1;
+    if (prep && prep[rm::TP_VALID] != 0.0f) {
+      #pragma unroll
+      for (int j = 0; j < KL; ++j) te[j] = j < ns ? __builtin_fmaxf(prep[rm::TP_G + j] * inv, 0.0f) : __builtin_huge_valf();
+      dl = prep[rm::TP_D0];
+      t = dl;
+      i0 = 2;
+    } else {
+      #pragma unroll
+      for (int j = 0; j < KL; ++j) te[j] = slot_init(j, ns);
+    }
+    temin = slot_min(te, ns);
+    return t <= T;
+  }
+
+  // Slot j's re-test at p = p(tt): the lower bound of its entry k from the entry's
+  // ball, and the slot's new expiry against pl = the planes' value + the slack, by the
+  // plane budget alone (as scene_lazy's re-test: rm_scene.hpp).
+  __device__ __forceinline__ void retest(const Table& S, int j, int k, f3 p, float pl, float tt) {
+#ifdef RM_TABLE_STATIC
+    const float* B = S.entry(k) + rm::TW_BALL;
+#else
+    const float4 B4 = reinterpret_cast<const float4*>(S.sb)[j];  // the slot's ball, staged
+    const float B[4] = {B4.x, B4.y, B4.z, RM_SBR(B4.w)};
+#endif
+    const float bx = p.x - B[0], by = p.y - B[1], bz = p.z - B[2];
+    const float lb = __builtin_fmaf(__builtin_amdgcn_sqrtf((bx * bx + by * by) + bz * bz),
+                                    1.0f - 0x1p-12f, -B[3]);
+    te[j] = vmax(__builtin_fmaf(lb - pl, invp, tt), te[j]);
+  }
+};
+
 template <int KL>
 __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflected, const float* prep) {
-  ro = topaque(ro);
+  ro = opaque(ro);
   const float* ex = S.exits();
   const int ns = S.n - 1, kp = S.n - 1;
   const float tmax = reflected ? 200.0f : 400.0f;
@@ -739,7 +783,7 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
   // (an SGPR operand takes a whole issue slot), other planes overwrite it (round 6:
   // -0.5 % per cfg3 frame, -1.5 % cfg2; the step's value no longer needs a copy
   // to merge two paths, profiles/r06_ab_tnu*.txt)
-  const float pw = topaque(S.fpw);
+  const float pw = opaque(S.fpw);
   auto plane = [&](float y) {
     float m = y + pw;
     if (!S.fpunit) m = S.plane_fast(mk(0.0f, y, 0.0f));
@@ -747,37 +791,13 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
   };
 #endif
   SLazy<KL> lz;
-  {
-    const float sig2 = 2.0f * ex[rm::EX_SIGMA];
-    const float rdl = __builtin_amdgcn_sqrtf(dot(rd, rd)) * (1.0f + 0x1p-16f);  // >= |rd|
-    const float rd1 = ((fabsf(rd.x) + fabsf(rd.y)) + fabsf(rd.z)) * (1.0f + 0x1p-16f);
-    const float ro1 = (fabsf(ro.x) + fabsf(ro.y)) + fabsf(ro.z);
-    lz.s0 = sig2 * (2.0f * ro1 + ex[rm::EX_S]) * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
-    lz.s1 = sig2 * rd1 * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
-    lz.inv = (1.0f - 0x1p-10f) *
-             __builtin_amdgcn_rcpf((1.0f + ex[rm::EX_LIP]) * rdl + sig2 * rd1) * (1.0f - 0x1p-16f);
-    // the plane's world normal is (0, n_y, 0): its slope along the ray is n_y rd.y
-    // (one rounding, far inside the 2^-8 added to s1)
-    const float ratep = (rdl + ex[rm::EX_PLANES + 1] * rd.y) + lz.s1 * (1.0f + 0x1p-8f);
-    lz.invp = ratep > 0.0f ? (1.0f - 0x1p-10f) * __builtin_amdgcn_rcpf(ratep) * (1.0f - 0x1p-16f) : 0.0f;
-    lz.idb = kp;
-  }
-  float t = 0.0f, dl = 0.0f;
-  int i0 = 1;  // sdf evaluations the first loop step brings the count to
-  if (prep && prep[rm::TP_VALID] != 0.0f) {
-    // step 0 at the camera, evaluated on the host (tmarch above); the gaps are
-    // TLazy's, their expiries at TLazy's rate
-    #pragma unroll
-    for (int j = 0; j < KL; ++j) lz.te[j] = j < ns ? __builtin_fmaxf(prep[rm::TP_G + j] * lz.inv, 0.0f) : __builtin_huge_valf();
-    dl = prep[rm::TP_D0];
-    t = dl;
-    i0 = 2;
-  } else {
-    #pragma unroll
-    for (int j = 0; j < KL; ++j) lz.te[j] = slot_init(j, ns);
-  }
-  lz.temin = slot_min(lz.te, ns);
-  if (!(t <= T)) return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+  // the plane's world normal is (0, n_y, 0): its slope along the ray is n_y rd.y
+  // (one rounding)
+  lz.rates(ex, ro, rd, [&] { return ex[rm::EX_PLANES + 1] * rd.y; });
+  lz.idb = kp;
+  float t, dl;
+  int i0;
+  if (!lz.seed(prep, ns, T, t, dl, i0)) return tmiss();
 
   // sdf(ro + rd t): the plane, and the block when some lane's expiry has passed
   auto step = [&](float tt) {
@@ -807,17 +827,7 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
           lz.te[j] = vmax(__builtin_fmaf(v - pl, lz.invp, tt), lz.te[j]);
           continue;
         }
-#ifdef RM_TABLE_STATIC
-        const float* B = S.entry(j) + rm::TW_BALL;
-#else
-        const float4 B4 = reinterpret_cast<const float4*>(S.sb)[j];  // the slot's ball, staged
-        const float B[4] = {B4.x, B4.y, B4.z, RM_SBR(B4.w)};
-#endif
-        const float bx = p.x - B[0], by = p.y - B[1], bz = p.z - B[2];
-        const float lb = __builtin_fmaf(__builtin_amdgcn_sqrtf((bx * bx + by * by) + bz * bz),
-                                        1.0f - 0x1p-12f, -B[3]);
-        // (the plane budget alone, as scene_lazy's re-test: rm_scene.hpp)
-        lz.te[j] = vmax(__builtin_fmaf(lb - pl, lz.invp, tt), lz.te[j]);
+        lz.retest(S, j, j, p, pl, tt);  // (slot j holds entry j)
         if (lz.te[j] <= tt) {  // opU in table order, later entries win ties
           const float v = prim_dist<kBoundedPoints>(S.entry(j), S.type(j), p, S.blend, S.omblend);
           idp = (v <= m) ? j : idp;
@@ -829,6 +839,10 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
     }
     return m;
   };
+  // The loop in this march's own text, and the same text again in gmarch: moved into one
+  // function over the step functor, the specialised kernels' code changed in size and
+  // instruction mix (profiles/dedupe_code_objects.txt), which the rule set for that
+  // change does not accept.
   float tp = t;
   auto run = [&](auto esc, auto useT) {
     if (!decltype(esc)::value && !decltype(useT)::value) {
@@ -879,7 +893,7 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
     asm volatile("" : "+v"(k));
     return THit{t, S.id(k), S.material(k), S.color(k, p), dl};
   }
-  return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+  return tmiss();
 }
 
 // ---- the block shape for any plane-bounded table (round 5) ----
@@ -903,7 +917,7 @@ __device__ __forceinline__ THit smarch(const Table& S, f3 ro, f3 rd, bool reflec
 //     the reference's sdf() at that point.
 template <int KL>
 __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflected, const float* prep) {
-  ro = topaque(ro);
+  ro = opaque(ro);
   const float* ex = S.exits();
   const int ns = (int)ex[rm::EX_NSLOTS];
   const int np = (int)ex[rm::EX_NPLANES];
@@ -912,39 +926,17 @@ __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflec
   const int nmax = reflected ? 256 : 512;
   const float T = table_exit_T(ex, MISS_C, 0.0f, ro, rd);
   SLazy<KL> lz;
-  {
-    const float sig2 = 2.0f * ex[rm::EX_SIGMA];
-    const float rdl = __builtin_amdgcn_sqrtf(dot(rd, rd)) * (1.0f + 0x1p-16f);  // >= |rd|
-    const float rd1 = ((fabsf(rd.x) + fabsf(rd.y)) + fabsf(rd.z)) * (1.0f + 0x1p-16f);
-    const float ro1 = (fabsf(ro.x) + fabsf(ro.y)) + fabsf(ro.z);
-    lz.s0 = sig2 * (2.0f * ro1 + ex[rm::EX_S]) * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
-    lz.s1 = sig2 * rd1 * ((1.0f + 0x1p-9f) * (1.0f + 0x1p-8f));
-    lz.inv = (1.0f - 0x1p-10f) *
-             __builtin_amdgcn_rcpf((1.0f + ex[rm::EX_LIP]) * rdl + sig2 * rd1) * (1.0f - 0x1p-16f);
+  lz.rates(ex, ro, rd, [&] {
     float smax = -__builtin_huge_valf();
     RM_TS_UNROLL
     for (int j = 0; j < rm::EX_MAX_PLANES; ++j)
       if (j < np) smax = fmaxf(smax, dot(rd, mk(ex[rm::EX_PLANES + 4 * j], ex[rm::EX_PLANES + 4 * j + 1],
                                                  ex[rm::EX_PLANES + 4 * j + 2])));
-    const float ratep = (rdl + smax) + lz.s1 * (1.0f + 0x1p-8f);
-    lz.invp = ratep > 0.0f ? (1.0f - 0x1p-10f) * __builtin_amdgcn_rcpf(ratep) * (1.0f - 0x1p-16f) : 0.0f;
-  }
-  float t = 0.0f, dl = 0.0f;
-  int i0 = 1;
-  if (prep && prep[rm::TP_VALID] != 0.0f) {
-    // step 0 at the camera, evaluated on the host (table_prep_host: slot j's gap
-    // with U = the planes at the camera), at TLazy's rate as in smarch
-    #pragma unroll
-    for (int j = 0; j < KL; ++j) lz.te[j] = j < ns ? __builtin_fmaxf(prep[rm::TP_G + j] * lz.inv, 0.0f) : __builtin_huge_valf();
-    dl = prep[rm::TP_D0];
-    t = dl;
-    i0 = 2;
-  } else {
-    #pragma unroll
-    for (int j = 0; j < KL; ++j) lz.te[j] = slot_init(j, ns);
-  }
-  lz.temin = slot_min(lz.te, ns);
-  if (!(t <= T)) return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+    return smax;
+  });
+  float t, dl;
+  int i0;
+  if (!lz.seed(prep, ns, T, t, dl, i0)) return tmiss();
 
   auto step = [&](float tt) {
     const f3 p = mk(ro.x + rd.x * tt, ro.y + rd.y * tt, ro.z + rd.z * tt);
@@ -980,16 +972,7 @@ __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflec
       #pragma unroll
       for (int j = 0; j < KL; ++j) {
         if (j >= ns || !wany(tt >= lz.te[j])) continue;
-#ifdef RM_TABLE_STATIC
-        const float* B = S.entry((int)ex[rm::EX_SLOTS + j]) + rm::TW_BALL;
-#else
-        const float4 B4 = reinterpret_cast<const float4*>(S.sb)[j];  // the slot's ball, staged
-        const float B[4] = {B4.x, B4.y, B4.z, RM_SBR(B4.w)};
-#endif
-        const float bx = p.x - B[0], by = p.y - B[1], bz = p.z - B[2];
-        const float lb = __builtin_fmaf(__builtin_amdgcn_sqrtf((bx * bx + by * by) + bz * bz),
-                                        1.0f - 0x1p-12f, -B[3]);
-        lz.te[j] = vmax(__builtin_fmaf(lb - pl, lz.invp, tt), lz.te[j]);
+        lz.retest(S, j, (int)ex[rm::EX_SLOTS + j], p, pl, tt);
         if (wany(lz.te[j] <= tt)) due |= 1u << j;
       }
       lz.temin = slot_min(lz.te, ns);
@@ -1009,9 +992,10 @@ __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflec
     }
     return m;
   };
+  // (smarch's loop, in this march's own text for the reason given there)
   float tp = t;
   auto run = [&](auto esc, auto useT) {
-    if (!decltype(esc)::value && !decltype(useT)::value) {  // (smarch's form)
+    if (!decltype(esc)::value && !decltype(useT)::value) {
       float dp = 0.0f;
       for (int i = i0;; ++i) {
         t = t + dp;
@@ -1049,7 +1033,7 @@ __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflec
     asm volatile("" : "+v"(k));  // (a 32-bit index: smarch's note)
     return THit{t, S.id(k), S.material(k), S.color(k, p), dl};
   }
-  return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+  return tmiss();
 }
 
 // RayMarch glsl:125-142 / reflectedRay glsl:144-161.  SL: the production
@@ -1057,7 +1041,7 @@ __device__ __forceinline__ THit gmarch(const Table& S, f3 ro, f3 rd, bool reflec
 // (any plane-bounded table): the generic kernel's instance, chosen on the host
 // (rm::table_shape); a specialised table's shape is a compile-time test.
 template <bool COUNT, int KL, int SL = 0>
-__device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected, TCnt& c,
+__device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected, Cnt& c,
                                    const float* prep = nullptr) {
 #ifdef RM_TABLE_STATIC
   if (!COUNT && slazy_table(S)) return smarch<KL>(S, ro, rd, reflected, prep);
@@ -1071,7 +1055,7 @@ __device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected
   // the generic kernel spills less (28 -> 12 B of scratch per lane): -2.9 % per
   // cfg3 frame (round 3).  The fast plane's parameters moved to
   // VGPRs the same way measured +0.5 % against this (more spills).
-  ro = topaque(ro);
+  ro = opaque(ro);
   const float tmax = reflected ? 200.0f : 400.0f;
   const int nmax = reflected ? 256 : 512;
   float t = 0.0f;
@@ -1104,7 +1088,7 @@ __device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected
     // the march ends on hit | escape | t + d past T (a NaN t + d fails the
     // compare; the reference would march on with t = NaN to the cap, also a
     // miss) | the step cap.  The last step's t is kept, so its hit test re-forms.
-    if (!(t <= T)) return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+    if (!(t <= T)) return tmiss();
     float tp = 0.0f, d = 0.0f;
     int k = 0;
     // Variants of the loop (as march<false>'s): the T compare is dropped when T
@@ -1155,7 +1139,7 @@ __device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected
       const f3 p = add(ro, muls(rd, tp));
       return THit{tp, S.id(k), S.material(k), S.color(k, p), d};
     }
-    return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+    return tmiss();
   }
   for (int i = i0; i < nmax; ++i) {
     if (t > T) {
@@ -1175,14 +1159,14 @@ __device__ RM_TS_INLINE THit tmarch(const Table& S, f3 ro, f3 rd, bool reflected
     if (d > tmax) break;
     t += d;
   }
-  return THit{-1.0f, -1, 1.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+  return tmiss();
 }
 
 // GetNormal glsl:278-288
 template <bool COUNT>
 // With have_c0 the centre sample sdf(pos) is c0, the march's last distance at
 // this very point (render's pos == the march's last p, glsl:226 vs :129).
-__device__ RM_TS_INLINE f3 tnormal(const Table& S, f3 pos, TCnt& c, bool have_c0 = false,
+__device__ RM_TS_INLINE f3 tnormal(const Table& S, f3 pos, Cnt& c, bool have_c0 = false,
                                    float c0 = 0.0f) {
   if (COUNT) c.normals++;
   float x, y, z;
@@ -1192,7 +1176,7 @@ __device__ RM_TS_INLINE f3 tnormal(const Table& S, f3 pos, TCnt& c, bool have_c0
 
 // softshadow glsl:201-216
 template <bool COUNT, int KL>
-__device__ RM_TS_INLINE float tshadow(const Frame& F, const Table& S, f3 ro, f3 rd, TCnt& c) {
+__device__ RM_TS_INLINE float tshadow(const Frame& F, const Table& S, f3 ro, f3 rd, Cnt& c) {
   float res = 1.0f, t = 0.0f;
   const float c_sh = F.shc;  // (1 + 2^-9) / k (1 + 2^-12), 0 for k = +inf (host, make_frame)
   const float T = table_exit_T(S.exits(), c_sh, 0.001f, ro, rd);
@@ -1216,7 +1200,7 @@ __device__ RM_TS_INLINE float tshadow(const Frame& F, const Table& S, f3 ro, f3 
 // the colour unchanged (glsl:181, 189-190): the loop stops there.
 template <bool COUNT, int KL, int SL = 0>
 __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3 pos, f3 normal, f3 color,
-                      const THit& primary, TCnt& c) {
+                      const THit& primary, Cnt& c) {
   float prevMat = primary.material;
   f3 prevColor = primary.color;
   const f3 lpos = mk(F.lpos[0], F.lpos[1], F.lpos[2]);
@@ -1226,7 +1210,7 @@ __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3
     THit h = tmarch<COUNT, KL, SL>(S, add(pos, muls(normal, 0.001f)), rayDir, true, c);
 #ifdef RM_TDBL_BMARCH
     if (!COUNT) {
-      const THit h2 = tmarch<COUNT, KL, SL>(S, topaque(add(pos, muls(normal, 0.001f))), rayDir, true, c);
+      const THit h2 = tmarch<COUNT, KL, SL>(S, opaque(add(pos, muls(normal, 0.001f))), rayDir, true, c);
       h.t = (h2.t == h.t) ? h.t : __builtin_nanf("");
     }
 #endif
@@ -1235,7 +1219,7 @@ __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3
     if (h.t != -1.0f || i < F.bounces) normal = tnormal<COUNT>(S, pos, c);
 #ifdef RM_TDBL_NORMAL
     if (!COUNT && (h.t != -1.0f || i < F.bounces)) {
-      const f3 n2 = tnormal<COUNT>(S, topaque(pos), c);
+      const f3 n2 = tnormal<COUNT>(S, opaque(pos), c);
       normal = mk(fminf(normal.x, n2.x), fminf(normal.y, n2.y), fminf(normal.z, n2.z));
     }
 #endif
@@ -1251,7 +1235,7 @@ __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3
     if (h.id == 7 && i < 3) {  // prevObject.material != MATTE here
       float sh = tshadow<COUNT, KL>(F, S, add(pos, muls(normal, 0.02f)), sub(lpos, pos), c);
 #ifdef RM_TDBL_SHADOW
-      if (!COUNT) sh = fminf(sh, tshadow<COUNT, KL>(F, S, topaque(add(pos, muls(normal, 0.02f))), sub(lpos, pos), c));
+      if (!COUNT) sh = fminf(sh, tshadow<COUNT, KL>(F, S, opaque(add(pos, muls(normal, 0.02f))), sub(lpos, pos), c));
 #endif
       color = muls(color, sh / (float)i);
     }
@@ -1265,12 +1249,12 @@ __device__ RM_TS_INLINE f3 tbounce(const Frame& F, const Table& S, f3 rayDir, f3
 // render glsl:218-251.  hit: where the primary hit goes besides (rm_scene.hpp NoHit /
 // GbufStore), called once: after the normal on a hit, after the march on a miss.
 template <bool COUNT, int KL, int SL = 0, class HIT = NoHit>
-__device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd, TCnt& c, HIT hit = HIT()) {
+__device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd, Cnt& c, HIT hit = HIT()) {
   f3 color = subs(mk(0.30f, 0.36f, 0.60f), rd.y * 0.2f);
   THit h = tmarch<COUNT, KL, SL>(S, ro, rd, false, c, F.prepv);
 #ifdef RM_TDBL_MARCH
   if (!COUNT) {
-    const THit h2 = tmarch<COUNT, KL, SL>(S, topaque(ro), rd, false, c, F.prepv);
+    const THit h2 = tmarch<COUNT, KL, SL>(S, opaque(ro), rd, false, c, F.prepv);
     h.t = (h2.t == h.t) ? h.t : __builtin_nanf("");
   }
 #endif
@@ -1282,7 +1266,7 @@ __device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd,
     f3 normal = tnormal<COUNT>(S, pos, c, true, h.d);
 #ifdef RM_TDBL_NORMAL
     if (!COUNT) {
-      const f3 n2 = tnormal<COUNT>(S, topaque(pos), c, true, h.d);
+      const f3 n2 = tnormal<COUNT>(S, opaque(pos), c, true, h.d);
       normal = mk(fminf(normal.x, n2.x), fminf(normal.y, n2.y), fminf(normal.z, n2.z));
     }
 #endif
@@ -1293,7 +1277,7 @@ __device__ RM_TS_INLINE f3 trender(const Frame& F, const Table& S, f3 ro, f3 rd,
       const f3 lpos = mk(F.lpos[0], F.lpos[1], F.lpos[2]);
       float sh = tshadow<COUNT, KL>(F, S, add(pos, muls(normal, 0.02f)), sub(lpos, pos), c);
 #ifdef RM_TDBL_SHADOW
-      if (!COUNT) sh = fminf(sh, tshadow<COUNT, KL>(F, S, topaque(add(pos, muls(normal, 0.02f))), sub(lpos, pos), c));
+      if (!COUNT) sh = fminf(sh, tshadow<COUNT, KL>(F, S, opaque(add(pos, muls(normal, 0.02f))), sub(lpos, pos), c));
 #endif
       return gamma(muls(color, sh));
     }
@@ -1351,15 +1335,6 @@ __device__ __forceinline__ Table stage(const Frame& F, float* lds) {
 #endif
 }
 
-__device__ __forceinline__ void flush_counts(const Frame& F, const TCnt& c) {
-  atomicAdd(&F.counters[0], (unsigned long long)c.rays);
-  atomicAdd(&F.counters[1], (unsigned long long)c.march);
-  atomicAdd(&F.counters[2], (unsigned long long)c.reflect);
-  atomicAdd(&F.counters[3], (unsigned long long)c.shadow);
-  atomicAdd(&F.counters[4], (unsigned long long)c.normals);
-  atomicAdd(&F.counters[5], (unsigned long long)c.lights);
-}
-
 // Waves per SIMD the register allocation must allow.  The per-table specialised
 // kernels (RM_TABLE_STATIC) get the bound from rm_jit.hip: the most waves at
 // which the table's code needs no scratch.  The generic kernel is latency bound
@@ -1375,16 +1350,6 @@ __device__ __forceinline__ void flush_counts(const Frame& F, const TCnt& c) {
 #define RM_TABLE_SL_WAVES 7
 #endif
 
-// The lane id re-formed after the march (v_mbcnt, one-wave workgroups: the same
-// value as threadIdx.x): the output pixel's coordinates and index come from it
-// instead of staying live across trender, where both table kernels spilled them
-// to scratch (5 VGPRs, round 5).  Volatile so that LLVM cannot fold it back onto
-// the prologue's threadIdx.x.
-__device__ __forceinline__ int out_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
 // Index in the launch's [rows][width] image of pixel (tx, ty) of tile (bx, by)
 // of `edge` x `edge` pixels.
 __device__ __forceinline__ size_t out_index(const Frame& F, int tx, int ty, int edge, int bx, int by) {
@@ -1405,7 +1370,7 @@ __device__ __forceinline__ void table_pixel_body(const Frame& F, float* lds, int
   if (px >= F.width || lrow >= F.rows) return;
   const size_t idx = (size_t)lrow * (size_t)F.width + (size_t)px;
   const int py = global_row(F, lrow);
-  TCnt c = {0, 0, 0, 0, 0, 0};
+  Cnt c = {0, 0, 0, 0, 0, 0};
   if (py < 0) {
     store_pixel(F, idx, 0.0f, 0.0f, 0.0f, 0.0f);
     if (GBUF) gbuf_store_miss(gbuf + 2 * idx);  // a shard's padding row
@@ -1440,7 +1405,7 @@ __device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, in
   const int lrow = by * 4 + (q >> 2);
   if (px >= F.width || lrow >= F.rows) return;  // the 4 lanes of a pixel leave together
   const int py = global_row(F, lrow);
-  TCnt c = {0, 0, 0, 0, 0, 0};
+  Cnt c = {0, 0, 0, 0, 0, 0};
   f3 col = mk(0.0f, 0.0f, 0.0f);
   if (py >= 0) {
     f3 ro, rd;
@@ -1452,9 +1417,7 @@ __device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, in
     else
       col = trender<COUNT, KL, SL>(F, S, ro, rd, c);
   }
-  const float r1 = __shfl(col.x, lane + 1), g1 = __shfl(col.y, lane + 1), b1 = __shfl(col.z, lane + 1);
-  const float r2 = __shfl(col.x, lane + 2), g2 = __shfl(col.y, lane + 2), b2 = __shfl(col.z, lane + 2);
-  const float r3 = __shfl(col.x, lane + 3), g3 = __shfl(col.y, lane + 3), b3 = __shfl(col.z, lane + 3);
+  const Quad nb = quad_neighbours(col, lane);
   uint32_t cnt = 0;
   if (COUNT) {
     const uint32_t mine = c.march + c.reflect + c.shadow + 4u * c.normals;
@@ -1467,9 +1430,8 @@ __device__ __forceinline__ void table_sample_body(const Frame& F, float* lds, in
   if ((ol & 3) != 0) return;
   const size_t at = out_index(F, (ol >> 2) & 3, ol >> 4, 4, bx, by);
   if (global_row(F, by * 4 + (ol >> 4)) >= 0) {
-    const float o0 = ((col.x + r1) + r2) + r3, o1 = ((col.y + g1) + g2) + g3,
-                o2 = ((col.z + b1) + b2) + b3;
-    store_pixel(F, at, o0 / 4.0f, o1 / 4.0f, o2 / 4.0f, 1.0f);
+    const f3 o = quad_sum(col, nb);
+    store_pixel(F, at, o.x / 4.0f, o.y / 4.0f, o.z / 4.0f, 1.0f);
   } else {
     store_pixel(F, at, 0.0f, 0.0f, 0.0f, 0.0f);
     if (GBUF) gbuf_store_miss(gbuf + 2 * at);  // a shard's padding row
@@ -1492,21 +1454,15 @@ __global__ __launch_bounds__(64, SL ? RM_TABLE_SL_WAVES : RM_TABLE_MIN_WAVES) vo
 // size and AA setting in one launch, each workgroup reading its frame's
 // constants from the batch in the kernel arguments.  The (y, z) workgroup slots
 // are read row-major over the frames, as k_sample_frames reads them
-// (rm_kernels.hip batch_slot: every frame's slowest rows first).  The bodies are
+// (rm_scene.hpp batch_slot: every frame's slowest rows first).  The bodies are
 // the kernels' above, so every frame is the image of its own dispatch.
 // Production kernels only (a batch collects no counters).
-__device__ __forceinline__ void table_batch_slot(int& frame, int& rowslot) {
-  const int L = blockIdx.z * gridDim.y + blockIdx.y, n = gridDim.z;
-  // uniform: kept in SGPRs (the division is VALU code)
-  rowslot = __builtin_amdgcn_readfirstlane(L / n);
-  frame = __builtin_amdgcn_readfirstlane(L - rowslot * n);
-}
 template <int KL = rm::EX_MAX_SLOTS, int SL = 0>
 __global__ __launch_bounds__(64, SL ? RM_TABLE_SL_WAVES : RM_TABLE_MIN_WAVES) void k_table_pixel_frames(
     FrameBatch B) {
   extern __shared__ float lds[];
   int f, r;
-  table_batch_slot(f, r);
+  batch_slot(f, r);
   table_pixel_body<false, KL, SL>(B.f[f], lds, r);
 }
 template <int KL = rm::EX_MAX_SLOTS, int SL = 0>
@@ -1514,7 +1470,7 @@ __global__ __launch_bounds__(64, SL ? RM_TABLE_SL_WAVES : RM_TABLE_MIN_WAVES) vo
     FrameBatch B) {
   extern __shared__ float lds[];
   int f, r;
-  table_batch_slot(f, r);
+  batch_slot(f, r);
   table_sample_body<false, KL, SL>(B.f[f], lds, r);
 }
 

@@ -39,20 +39,20 @@ struct TableFast {
   const Frame& F;
   const Table S;
   __device__ __forceinline__ FastHit march(f3 ro, f3 rd, bool reflected) const {
-    TCnt c = {0, 0, 0, 0, 0, 0};
+    Cnt c = {0, 0, 0, 0, 0, 0};
     const THit h = tmarch<false, KL, 0>(S, ro, rd, reflected, c);
     return FastHit{h.t, h.id, h.material, h.color, h.d};
   }
   __device__ __forceinline__ f3 normal(f3 pos, float d) const {
-    TCnt c = {0, 0, 0, 0, 0, 0};
+    Cnt c = {0, 0, 0, 0, 0, 0};
     return tnormal<false>(S, pos, c, true, d);
   }
   __device__ __forceinline__ float shadow(f3 ro, f3 rd) const {
-    TCnt c = {0, 0, 0, 0, 0, 0};
+    Cnt c = {0, 0, 0, 0, 0, 0};
     return tshadow<false, KL>(F, S, ro, rd, c);
   }
   __device__ __forceinline__ f3 render(f3 ro, f3 rd) const {
-    TCnt c = {0, 0, 0, 0, 0, 0};
+    Cnt c = {0, 0, 0, 0, 0, 0};
     return trender<false, KL, 0>(F, S, ro, rd, c);
   }
   // The table term of the predicate for RM_TRACE_SHADOW.

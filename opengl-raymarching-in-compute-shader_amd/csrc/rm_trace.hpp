@@ -67,7 +67,7 @@ __device__ __forceinline__ void trace_store(float4* hits, int64_t i, const Trace
 // ---- the fast path ---------------------------------------------------------------------
 // What a query family calls on a lane inside its predicate: the render kernels'
 // device code, proofs and all, in the instantiations the adapters name.  Every
-// call holds its own work counter (Cnt / TCnt: no counting build).
+// call holds its own work counter (Cnt / Cnt: no counting build).
 // Fast: FastHit march(f3 ro, f3 rd, bool reflected) const
 //       f3 normal(f3 pos, float d) const    GetNormal at a march's hit, d its last distance (the centre sample),
 //       float shadow(f3 ro, f3 rd) const    softshadow,

@@ -6,10 +6,11 @@ gfx950 with the probes tools/ uses: RM_STATS (tools/stats_probe.py), RM_WAVE_TIM
 via tools/build_variant.sh), and rm_table.hip with its RM_TDBL_<PHASE> probes.
 Device-only compiles: no GPU needed."""
 import os
-import shutil
 import subprocess
 
 import pytest
+
+from code_objects import OBJDUMP, built_descriptors, field
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "csrc")
@@ -35,8 +36,6 @@ def test_diagnostic_build_compiles(name, tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
 
 
-BUILD = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "build")
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 # Scratch bytes per lane each production kernel may use: none for the built-in
 # kernels; the generic table kernel's batch kernels (every production frame since
 # round 6, a single one as a batch of one) none in the 5-slot instances, 8 B in
@@ -57,17 +56,7 @@ SCRATCH_MAX = {"7k_pixelILb0E": 0, "8k_sampleILb0E": 0, "14k_pixel_frames": 0,
 def test_production_kernels_scratch(obj, tmp_path):
     """The in-tree build's gfx950 code objects (make librm, __graft_entry__.build):
     the private segment of every production kernel, from its kernel descriptor."""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from test_scene_table import _kernel_private_sizes
-    src = os.path.join(BUILD, obj)
-    if not os.path.exists(src):
-        pytest.skip("librm not built")
-    shutil.copy(src, tmp_path / "x.o")
-    subprocess.run([OBJDUMP, "--offloading", "x.o"], cwd=tmp_path, capture_output=True, check=True)
-    cos = [p for p in os.listdir(tmp_path) if "gfx950" in p]
-    assert len(cos) == 1, os.listdir(tmp_path)
-    priv = _kernel_private_sizes(open(tmp_path / cos[0], "rb").read())
+    priv = field(built_descriptors(obj, tmp_path), "scratch")
     if obj == "rm_table.o":  # production frames are batches (of one): no single-frame production kernels
         assert not any("k_table_sampleILb0E" in k or "k_table_pixelILb0E" in k for k in priv), priv
     seen = 0

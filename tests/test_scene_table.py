@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from code_objects import field, kernel_descriptors
+
 
 def test_default_scene_is_the_reference_scene(rm):
     sc = rm.default_scene()
@@ -103,30 +105,6 @@ def _code_object(rm, scene, arch=b"gfx950"):
     return out
 
 
-def _kernel_private_sizes(co):
-    """private_segment_fixed_size (scratch bytes per lane; u32 at offset 4 of the
-    64-byte kernel descriptor `<kernel>.kd`) of every kernel in an AMDGPU ELF."""
-    import struct
-    shoff, = struct.unpack_from("<Q", co, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQIIQQ", co, shoff + i * shentsize) for i in range(shnum)]
-    out = {}
-    for name_, type_, flags, addr, off, size, link, info, align, entsize in secs:
-        if type_ != 2:  # SHT_SYMTAB
-            continue
-        stroff = secs[link][4]
-        for k in range(size // 24):
-            st_name, st_info, st_other, st_shndx, st_value, st_size = struct.unpack_from(
-                "<IBBHQQ", co, off + 24 * k)
-            end = co.index(b"\0", stroff + st_name)
-            sym = co[stroff + st_name:end].decode()
-            if sym.endswith(".kd") and st_shndx < shnum:
-                sec = secs[st_shndx]
-                kd = sec[4] + (st_value - sec[3])
-                out[sym[:-3]] = struct.unpack_from("<I", co, kd + 4)[0]
-    return out
-
-
 def test_table_specialises_without_a_device(rm):
     """rm_scene_specialize's hiprtc compile (rm_jit.hip) runs here, without a GPU:
     the embedded rm_table.hip compiles for gfx950 with the table folded in, and
@@ -141,7 +119,7 @@ def test_table_specialises_without_a_device(rm):
     for name in (b"k_table_pixelILb1E", b"k_table_sampleILb1E", b"k_table_pixel_frames",
                  b"k_table_sample_frames"):
         assert name in co
-    priv = _kernel_private_sizes(co)
+    priv = field(kernel_descriptors(co), "scratch")
     # the single-frame production kernels are not compiled (they spilled 12 B)
     assert not any("ILb0E" in k for k in priv), priv
     prod = {k: v for k, v in priv.items() if "_frames" in k}
@@ -183,7 +161,7 @@ def test_table_compiles_once(rm, tmp_path):
     assert len(bound) == 2 and all("_frames" in x and " 0 B scratch" in x for x in bound), out.stderr
     rc, co = _code_object(rm, rm.default_scene())
     assert rc == 0
-    vg = _kernel_vgprs(co)
+    vg = field(kernel_descriptors(co), "vgprs")
     prod = {k: v for k, v in vg.items() if "_frames" in k}
     assert len(prod) == 2 and all(v <= 64 for v in prod.values()), vg  # 8 waves per SIMD
 
@@ -211,27 +189,3 @@ def test_large_tables_are_not_compiled(rm):
                          capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "hiprtc compile" not in out.stderr, out.stderr
-
-
-def _kernel_vgprs(co):
-    """VGPR allocation per lane of every kernel (compute_pgm_rsrc1 bits 5:0 of its
-    descriptor at offset 48: allocation / 8 - 1 on gfx950)."""
-    import struct
-    shoff, = struct.unpack_from("<Q", co, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", co, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQIIQQ", co, shoff + i * shentsize) for i in range(shnum)]
-    out = {}
-    for name_, type_, flags, addr, off, size, link, info, align, entsize in secs:
-        if type_ != 2:
-            continue
-        stroff = secs[link][4]
-        for k in range(size // 24):
-            st_name, st_info, st_other, st_shndx, st_value, st_size = struct.unpack_from(
-                "<IBBHQQ", co, off + 24 * k)
-            end = co.index(b"\0", stroff + st_name)
-            sym = co[stroff + st_name:end].decode()
-            if sym.endswith(".kd") and st_shndx < shnum:
-                sec = secs[st_shndx]
-                kd = sec[4] + (st_value - sec[3])
-                out[sym[:-3]] = ((struct.unpack_from("<I", co, kd + 48)[0] & 0x3F) + 1) * 8
-    return out

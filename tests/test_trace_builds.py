@@ -3,30 +3,14 @@ k_trace and k_table_trace use no scratch memory (their kernel descriptors'
 private segment), and live in objects of their own, so the render kernels'
 objects hold no trace kernel."""
 import os
-import shutil
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "build")
-OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+from code_objects import BUILD, OBJDUMP, built_descriptors, field
 
 
 def _private_sizes(obj, tmp_path):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from test_scene_table import _kernel_private_sizes
-    src = os.path.join(BUILD, obj)
-    if not os.path.exists(src):
-        pytest.skip("librm not built")
-    d = tmp_path / obj
-    d.mkdir()
-    shutil.copy(src, d / "x.o")
-    subprocess.run([OBJDUMP, "--offloading", "x.o"], cwd=d, capture_output=True, check=True)
-    cos = [p for p in os.listdir(d) if "gfx950" in p]
-    assert len(cos) == 1, os.listdir(d)
-    return _kernel_private_sizes(open(d / cos[0], "rb").read())
+    return field(built_descriptors(obj, tmp_path), "scratch")
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
