@@ -8,6 +8,12 @@ from adaptive_model import flag_mask
 
 COLOR, ID, DEPTH, NORMAL, ALBEDO = 1, 2, 4, 8, 16
 F32 = np.float32
+BITS = {"ID": ID, "DEPTH": DEPTH, "NORMAL": NORMAL, "ALBEDO": ALBEDO}
+# (width, height) -> flagged pixels per criterion alone, at depth_rel 0.05 and normal_cos 0.9, on the
+# oracle's G-buffer of rm_sweep_uniforms(60, 120, 1, 0, 0) (tests/test_adaptive_edges_model.py)
+COUNTS = {(130, 67): {"ID": 681, "DEPTH": 1921, "NORMAL": 376, "ALBEDO": 3624},
+          (37, 23): {"ID": 189, "DEPTH": 439, "NORMAL": 134, "ALBEDO": 545},
+          (9, 5): {"ID": 21, "DEPTH": 28, "NORMAL": 7, "ALBEDO": 37}}
 
 
 def _pairs(g, edges, depth_rel, normal_cos, axis):

@@ -68,3 +68,8 @@ def built_descriptors(obj, tmp_path):
 def field(kd, name):
     """{kernel: its descriptor's field `name`}."""
     return {k: v[name] for k, v in kd.items()}
+
+
+def private_sizes(obj, tmp_path):
+    """{kernel: scratch bytes per lane} of the in-tree build's object `obj`."""
+    return field(built_descriptors(obj, tmp_path), "scratch")

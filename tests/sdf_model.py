@@ -16,6 +16,8 @@ import ctypes.util
 
 import numpy as np
 
+from records import bits_equal  # noqa: F401  (M.bits_equal: tests/test_sdf_model.py, tools/stress_sdf.py)
+
 F32 = np.float32
 _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
 _libm.sinf.restype = C.c_float
@@ -184,14 +186,3 @@ def oracle_records(rm, O, u, pos, normal=False):
         _cache[key] = out
     return _cache[key]
 
-
-def bits_equal(a, b, what=""):
-    """Equal as uint32; a NaN counts as equal to a NaN (test_gpu_trace.bits_equal, for the
-    CPU tests, which cannot import a gpu-marked module's helpers without its imports)."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype.itemsize == 4 and b.dtype.itemsize == 4, (what, a.shape, b.shape)
-    same = a.view(np.uint32) == b.view(np.uint32)
-    if a.dtype.kind == "f" and b.dtype.kind == "f":
-        same |= np.isnan(a) & np.isnan(b)
-    bad = np.argwhere(~same)
-    assert len(bad) == 0, f"{what}: {len(bad)} differ, first at {bad[0]}: {a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}"

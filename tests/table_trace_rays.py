@@ -17,14 +17,15 @@ placed with the oracle's rmo_sdf_points at the default uniforms with iTime = 1.
                 2^11, 2^12: both borders of trace_fast_ok exactly;
   border    32  just outside it: |rd| = 2^-12 (1 - 2^-10), 2^12 (1 + 2^-10), and |ro|_1
                 one step above and below 2^20, aimed at the scene;
-  edge       9  test_gpu_trace.edge_rays(): zero, NaN, huge and infinite rays.
+  edge       9  tests/records.py edge_rays(): zero, NaN, huge and infinite rays.
 """
 import ctypes as C
 
 import numpy as np
 
-from test_gpu_scene import _big_table, floor_last_scene, random_scene
-from test_gpu_trace import edge_rays
+from records import edge_rays
+from scenes import scene_of as table  # T.table(rm, name): the table of that name, with its own ids
+from uniforms import default_u
 
 F32 = np.float32
 
@@ -38,18 +39,7 @@ AXES = np.array([(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0,
                  (1, 0, 1), (1, 0, -1), (-1, 0, 1), (-1, 0, -1)], F32)
 BOX_LO, BOX_HI = (-30.0, -8.0, -45.0), (30.0, 20.0, 12.0)
 
-_tables, _rays = {}, {}
-
-
-def table(rm, name):
-    """The table of that name, with its own ids (id 7 carries the shadow rule)."""
-    if name not in _tables:
-        k = int(name[-1])
-        _tables[name] = (random_scene(rm, k) if name.startswith("random")
-                         else random_scene(rm, 20 + k, nplanes=1 + k) if name.startswith("planes")
-                         else floor_last_scene(rm, k) if name.startswith("floor")
-                         else _big_table(rm, int(name[-2:])))
-    return _tables[name]
+_rays = {}
 
 
 def indexed(rm, scene):
@@ -65,9 +55,7 @@ def indexed(rm, scene):
 
 
 def placement_uniforms(rm):
-    u = rm.default_uniforms()
-    u.iTime = 1.0
-    return u
+    return default_u(rm)
 
 
 def fast_ok(o, d):

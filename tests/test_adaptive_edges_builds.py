@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from test_trace_builds import OBJDUMP, _private_sizes
+from code_objects import OBJDUMP, private_sizes
 
 KERNEL = "22k_adapt_classify_edges"
 OTHERS = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
@@ -15,7 +15,7 @@ OTHERS = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_tab
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
 def test_edge_classifier_uses_no_scratch(tmp_path):
-    priv = _private_sizes("rm_adaptive_edges.o", tmp_path)
+    priv = private_sizes("rm_adaptive_edges.o", tmp_path)
     assert len(priv) == 2, priv  # the two-pair form (ILb1E) and the plain one (ILb0E)
     assert all(KERNEL in name for name in priv), priv
     assert [n for n in priv if "ILb1E" in n] and [n for n in priv if "ILb0E" in n], priv
@@ -25,5 +25,5 @@ def test_edge_classifier_uses_no_scratch(tmp_path):
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
 @pytest.mark.parametrize("obj", OTHERS)
 def test_other_objects_do_not_hold_it(obj, tmp_path):
-    priv = _private_sizes(obj, tmp_path)
+    priv = private_sizes(obj, tmp_path)
     assert priv and not [k for k in priv if "classify_edges" in k], priv

@@ -6,42 +6,13 @@ the kernel's mask with the same model.  No GPU needed."""
 import numpy as np
 import pytest
 
-from adaptive_edges_model import ALBEDO, COLOR, DEPTH, ID, NORMAL, edge_mask
+from adaptive_edges_model import ALBEDO, BITS, COLOR, COUNTS, DEPTH, ID, NORMAL, edge_mask
+from records import oracle_gbuffer
+from uniforms import main_u
 
 F32 = np.float32
 GEOMETRY = ID | DEPTH | NORMAL | ALBEDO
-BITS = {"ID": ID, "DEPTH": DEPTH, "NORMAL": NORMAL, "ALBEDO": ALBEDO}
-# (width, height) -> flagged pixels per criterion alone, at depth_rel 0.05 and normal_cos 0.9
-COUNTS = {(130, 67): {"ID": 681, "DEPTH": 1921, "NORMAL": 376, "ALBEDO": 3624},
-          (37, 23): {"ID": 189, "DEPTH": 439, "NORMAL": 134, "ALBEDO": 545},
-          (9, 5): {"ID": 21, "DEPTH": 28, "NORMAL": 7, "ALBEDO": 37}}
 MISSES_130x67 = 3565  # tests/test_gpu_gbuffer.py MISSES[False]
-
-_gbufs = {}
-
-
-def oracle_gbuffer(rm, oracle, W, H):
-    """Every pixel's centre-ray hit, as tests/test_gpu_gbuffer.py builds it: cast_ray, raymarch,
-    get_normal at ro + rd * t in float32; a miss is t -1, id -1, zeros."""
-    if (W, H) not in _gbufs:
-        u = rm.sweep_uniforms(60, 120, 1, False, 0)
-        g = np.zeros((H, W), rm.GBUFFER_DTYPE)
-        for py in range(H):
-            for px in range(W):
-                uvx = F32(px * 2 - W) / F32(W)  # glsl:301-305, in float32
-                uvy = F32(py * 2 - H) / F32(H)
-                o, d = oracle.cast_ray(u, float(uvx), float(uvy))
-                h, _ = oracle.raymarch(u, o, d, False)
-                r = g[py, px]
-                r["t"], r["id"], r["albedo"] = h.hitpoint, h.id, tuple(h.color)
-                if r["t"] != F32(-1.0):
-                    pos = o + d * r["t"]
-                    assert pos.dtype == F32
-                    r["normal"] = oracle.get_normal(u, pos)
-        g.setflags(write=False)
-        _gbufs[(W, H)] = g
-    return _gbufs[(W, H)]
-
 
 def records(rm, rows):
     """A (1, len(rows)) G-buffer of (t, id, normal, albedo) tuples."""
@@ -108,7 +79,7 @@ def test_a_hit_beside_a_miss_flags_under_id_only(rm):
 @pytest.mark.parametrize("W,H", sorted(COUNTS))
 def test_the_mask_is_symmetric(rm, oracle, W, H):
     """If q flags p, p flags q: a flagged pixel has a flagged 4-neighbour."""
-    g = oracle_gbuffer(rm, oracle, W, H)
+    g = oracle_gbuffer(rm, oracle, main_u(rm), W, H)
     for edges in list(BITS.values()) + [GEOMETRY]:
         m = edge_mask(g, None, edges).astype(bool)
         n = np.zeros_like(m)
@@ -122,7 +93,7 @@ def test_the_mask_is_symmetric(rm, oracle, W, H):
 
 
 def test_one_pixel_has_no_neighbour(rm, oracle):
-    g = oracle_gbuffer(rm, oracle, 130, 67)[33:34, 60:61]
+    g = oracle_gbuffer(rm, oracle, main_u(rm), 130, 67)[33:34, 60:61]
     img = np.full((1, 1, 4), 200, np.uint8)
     for edges in (COLOR, ID, DEPTH, NORMAL, ALBEDO, GEOMETRY | COLOR):
         assert edge_mask(g, img, edges, 0, 0.0, 1.0).sum() == 0
@@ -130,7 +101,7 @@ def test_one_pixel_has_no_neighbour(rm, oracle):
 
 @pytest.mark.parametrize("W,H", sorted(COUNTS))
 def test_infinite_depth_rel_flags_nothing(rm, oracle, W, H):
-    g = oracle_gbuffer(rm, oracle, W, H)
+    g = oracle_gbuffer(rm, oracle, main_u(rm), W, H)
     assert edge_mask(g, None, DEPTH, depth_rel=float("inf")).sum() == 0
     assert edge_mask(g, None, DEPTH, depth_rel=0.0).sum() >= COUNTS[(W, H)]["DEPTH"]  # (a wider net)
 
@@ -138,7 +109,7 @@ def test_infinite_depth_rel_flags_nothing(rm, oracle, W, H):
 # ---- the oracle's G-buffer ---------------------------------------------------------------------
 @pytest.mark.parametrize("W,H", sorted(COUNTS))
 def test_counts_on_the_oracle_gbuffer(rm, oracle, W, H):
-    g = oracle_gbuffer(rm, oracle, W, H)
+    g = oracle_gbuffer(rm, oracle, main_u(rm), W, H)
     assert not np.isnan(g["normal"]).any()
     got = {k: int(edge_mask(g, None, b, depth_rel=0.05, normal_cos=0.9).sum()) for k, b in BITS.items()}
     print(f"{W}x{H}: {got}")
@@ -152,7 +123,7 @@ def test_counts_on_the_oracle_gbuffer(rm, oracle, W, H):
 
 
 def test_union_is_the_union(rm, oracle):
-    g = oracle_gbuffer(rm, oracle, 37, 23)
+    g = oracle_gbuffer(rm, oracle, main_u(rm), 37, 23)
     each = [edge_mask(g, None, b) for b in BITS.values()]
     assert (edge_mask(g, None, GEOMETRY) == np.bitwise_or.reduce(each)).all()
     img = np.zeros((23, 37, 4), np.uint8)

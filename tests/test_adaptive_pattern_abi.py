@@ -87,7 +87,7 @@ def test_the_gpu_tests_edges_cases_are_not_vacuous(rm, oracle):
     import numpy as np
     from adaptive_edges_model import COLOR, DEPTH, ID, NORMAL, edge_mask
     from adaptive_model import flag_mask
-    from test_gpu_scene import random_scene
+    from scenes import random_scene
     for W, H in [(130, 67), (37, 23), (9, 5), (8, 8)]:
         g = _oracle_gbuffer(rm, oracle, W, H, None)
         n = int(edge_mask(g, None, ID | DEPTH | NORMAL).sum())

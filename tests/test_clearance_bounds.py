@@ -20,7 +20,7 @@ this pins the geometry and the constants.  CPU only.
 """
 import numpy as np
 
-from test_fuzz_tables import _sdf64
+from scene_words import sdf64
 
 BLENDS = (0.0, 0.3, 1.0)  # the blend's weight: box, between, sphere
 
@@ -35,7 +35,7 @@ def _each(rm, p, blend):
     """[5][n]: the bounded primitives' distances, the blend at weight `blend`."""
     out = []
     for q in _prims(rm):
-        d = _sdf64(p, q, blend)
+        d = sdf64(p, q, blend)
         out.append(d[0] if len(d) == 1 else d[0] * (1.0 - blend) + d[1] * blend)
     return np.array(out)
 

@@ -14,7 +14,7 @@ The kernels' float roundings of the same bounds are covered by their margins
 import numpy as np
 import pytest
 
-from test_fuzz_tables import _sdf64
+from scene_words import EX_BOX, EX_VALID, TABLE_WORDS, as_f32, sdf64
 
 C = np.array([-5.0, 0.0, -10.0])
 R_ALL = 23.001
@@ -26,7 +26,7 @@ def _objects(rm, p):
     sphere, which bounds every blend weight in [0, 1])."""
     prims = [q for q in rm.default_scene() if q.type != rm.PRIM_PLANE]
     assert len(prims) == 5
-    return np.min([np.min(_sdf64(p, q, 0.5), axis=0) for q in prims], axis=0)
+    return np.min([np.min(sdf64(p, q, 0.5), axis=0) for q in prims], axis=0)
 
 
 def test_ball_and_slab_bound_the_objects(rm):
@@ -73,13 +73,12 @@ _BOX_CASES = [
 @pytest.mark.parametrize("swz", [0, 1])
 @pytest.mark.parametrize("case", range(len(_BOX_CASES)))
 def test_exit_box_holds_every_solid(rm, case, swz):
-    from test_fuzz_tables import EX_BOX, EX_VALID, TABLE_WORDS, _f
     t, param = _BOX_CASES[case]
     center = (-4.0, 1.5, -9.0)
     prim = rm.primitive(t, center, param, (0.5, 0.5, 0.5), id=1, swizzle=swz)
     floor = rm.primitive(rm.PRIM_PLANE, (0.0, 0.0, 0.0), (0.0, 1.0, 0.0, 5.5), id=7, material=0.0)
     w = rm.scene_words([prim, floor])
-    hdr = _f(w[2 * TABLE_WORDS:]).astype(np.float64)
+    hdr = as_f32(w[2 * TABLE_WORDS:]).astype(np.float64)
     if hdr[EX_VALID] != 1.0:
         pytest.skip("the host gives this table no exit bounds (exits off): nothing to check")
     lo, hi = hdr[EX_BOX:EX_BOX + 3], hdr[EX_BOX + 3:EX_BOX + 6]
@@ -90,7 +89,7 @@ def test_exit_box_holds_every_solid(rm, case, swz):
     p = np.array(center) + np.concatenate([rng.uniform(-e, e, (200_000, 3)) for e in (ext, ext / 4, ext / 16)])
     # a blend is inside for some weight (sin(iTime) moves it) where its box or its
     # sphere is: the box must hold both
-    d = np.min(_sdf64(p, prim, 0.5), axis=0)
+    d = np.min(sdf64(p, prim, 0.5), axis=0)
     inside = p[d <= 0.0]
     empty = ((t == 0 and param[0] <= 0.0) or (t == 1 and min(param[:3]) <= 0.0)
              or (t == 2 and min(param[:3]) <= 0.0 and param[3] <= 0.0)
@@ -104,5 +103,5 @@ def test_exit_box_holds_every_solid(rm, case, swz):
     # outside the box: every blend weight's distance is at least the slab distance
     slab = np.maximum(p - hi, lo - p).max(-1)
     out = slab > 0
-    dmin = np.min(_sdf64(p[out], prim, 0.5), axis=0)
+    dmin = np.min(sdf64(p[out], prim, 0.5), axis=0)
     assert (dmin >= slab[out] - 1e-9 * (1.0 + slab[out])).all()

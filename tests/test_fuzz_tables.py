@@ -13,10 +13,8 @@ hyp = pytest.importorskip("hypothesis")
 from hypothesis import HealthCheck, given, settings  # noqa: E402
 from hypothesis import strategies as st  # noqa: E402
 
-TABLE_WORDS, TW_TYPE, TW_BALL = 24, 0, 20
-EX_VALID, EX_CX, EX_R, EX_NPLANES = 0, 1, 4, 7
-EX_LIP, EX_NSLOTS, EX_EVAL_MASK, EX_PLANE_MASK, EX_SLOTS, EX_BOX, EXIT_WORDS = 24, 25, 26, 27, 28, 36, 42
-PLANE = 5
+from scene_words import (EX_BOX, EX_CX, EX_EVAL_MASK, EX_LIP, EX_NPLANES, EX_NSLOTS, EX_PLANE_MASK,  # noqa: E402
+                         EX_R, EX_SLOTS, EX_VALID, EXIT_WORDS, PLANE, TABLE_WORDS, TW_BALL, TW_TYPE, as_f32, sdf64)
 
 f32_any = st.floats(width=32, allow_nan=True, allow_infinity=True)
 f32_mid = st.floats(-60.0, 60.0, width=32)
@@ -58,14 +56,10 @@ def _words(rm, prims):
         return None
 
 
-def _f(w):
-    return w.view(np.float32)
-
-
 def _well_formed(prims, w):
     n = len(prims)
     assert w.shape == (n * TABLE_WORDS + EXIT_WORDS,)
-    hdr = _f(w[n * TABLE_WORDS:])
+    hdr = as_f32(w[n * TABLE_WORDS:])
     assert hdr[EX_VALID] in (0.0, 1.0)
     ns = int(hdr[EX_NSLOTS])
     assert 0 <= ns <= 8 and hdr[EX_NSLOTS] == ns
@@ -79,7 +73,7 @@ def _well_formed(prims, w):
     for k in range(n):
         e = w[k * TABLE_WORDS:(k + 1) * TABLE_WORDS]
         assert int(e[TW_TYPE]) == prims[k].type
-        ball = _f(e[TW_BALL:TW_BALL + 4])
+        ball = as_f32(e[TW_BALL:TW_BALL + 4])
         if hdr[EX_VALID] == 0.0 or prims[k].type == PLANE:
             assert ball[3] == np.inf, "no bound: never culled"
         else:
@@ -101,27 +95,6 @@ def test_any_table_is_refused_or_well_formed(rm, data):
         _well_formed(prims, w)
 
 
-def _sdf64(p, prim, blend):
-    """One entry's distance in float64 (glsl:83-103, 115-121), q = swizzle(p - c)."""
-    q = p - np.array(prim.center[:], np.float64)
-    if prim.swizzle == 1:
-        q = q[:, [0, 2, 1]]
-    a = np.array(prim.param[:], np.float64)
-    L = lambda v: np.sqrt((v * v).sum(-1))  # noqa: E731
-    if prim.type == 0:
-        return [L(q) - a[0]]
-    if prim.type in (1, 2):
-        d = np.abs(q) - a[:3]
-        box = np.minimum(d.max(-1), 0.0) + L(np.maximum(d, 0.0))
-        return [box] if prim.type == 1 else [box, L(q) - a[3]]  # a blend lies between the two
-    if prim.type == 3:
-        l2 = np.stack([L(q[:, [0, 2]]) - a[0], q[:, 1]], -1)
-        return [L(l2) - a[1]]
-    pa, ba = q - a[:3], a[3:6] - a[:3]
-    h = np.clip((pa * ba).sum(-1) / (ba * ba).sum(), 0.0, 1.0)
-    return [L(pa - ba * h[:, None]) - a[6]]
-
-
 @settings(max_examples=250, deadline=None, suppress_health_check=list(HealthCheck))
 @given(data=st.data())
 def test_culling_balls_bound_every_entry(rm, data):
@@ -134,7 +107,7 @@ def test_culling_balls_bound_every_entry(rm, data):
     assert w is not None
     _well_formed(prims, w)
     n = len(prims)
-    hdr = _f(w[n * TABLE_WORDS:]).astype(np.float64)
+    hdr = as_f32(w[n * TABLE_WORDS:]).astype(np.float64)
     if hdr[EX_VALID] != 1.0:
         return
     rng = np.random.default_rng(data.draw(st.integers(0, 2 ** 32 - 1)))
@@ -145,9 +118,9 @@ def test_culling_balls_bound_every_entry(rm, data):
     for k, prim in enumerate(prims):
         if prim.type == PLANE:
             continue
-        ball = _f(w[k * TABLE_WORDS + TW_BALL:k * TABLE_WORDS + TW_BALL + 4]).astype(np.float64)
+        ball = as_f32(w[k * TABLE_WORDS + TW_BALL:k * TABLE_WORDS + TW_BALL + 4]).astype(np.float64)
         lb = np.sqrt(((p - ball[:3]) ** 2).sum(-1)) - ball[3]
-        for d in _sdf64(p, prim, 0.5):
+        for d in sdf64(p, prim, 0.5):
             ok = d >= lb - 1e-9 * (1.0 + np.abs(lb))
             assert ok.all(), (k, prim.type, (lb - d).max())
             ok = d >= slab - 1e-9 * (1.0 + np.abs(slab))

@@ -2,10 +2,11 @@
 _device, rm_read_aa_mask, rm_get_aa_mask, rm_aa_refined).
 
 Throughout, A is rm_dispatch with AA off and B rm_dispatch with AA on, on a plain
-context with both colour outputs; C and M are the adaptive frame and its mask.  The
-definition: M is the flagging rule (tests/adaptive_model.py) applied to A's RGBA8
-image, or the caller's mask normalised to 0 / 1, and C is where(M, B, A), byte for
-byte in RGBA8 and bit for bit (as uint32) in RGBA32F.
+context with both colour outputs (tests/frames.py refs); C and M are the adaptive frame
+and its mask.  The definition (tests/adaptive_checks.py check_frame): M is the flagging
+rule (tests/adaptive_model.py) applied to A's RGBA8 image, or the caller's mask normalised
+to 0 / 1, and C is where(M, B, A), byte for byte in RGBA8 and bit for bit (as uint32) in
+RGBA32F.
 
 Main frame: rm_sweep_uniforms(60, 120, 1, ., 0) at 130 x 67: ragged for the 8x8 tiles
 and for the refinement's groups of 16, and its primary rays hit every object id.
@@ -15,67 +16,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from adaptive_checks import ADAPTIVE_CALLS, caller_masks, check_frame, expected, refused
 from adaptive_model import flag_mask
-from test_gpu_scene import floor_last_scene, random_scene
+from frames import BOTH, ab, images, refs, renderer
+from scenes import scene_of
+from uniforms import main_u, off_sweep_uniforms, with_aa
 
 pytestmark = pytest.mark.gpu
 
 W0, H0 = 130, 67
 SHAPES = [(130, 67), (37, 23), (9, 5), (1, 1)]
-BOTH = 3  # RM_OUT_RGBA8 | RM_OUT_RGBA32F
-
-
-def with_aa(u, aa):
-    v = type(u).from_buffer_copy(u)
-    v.AA = 1 if aa else 0
-    return v
-
-
-def main_u(rm, bounces=1, shadow=0, aa=False):
-    return rm.sweep_uniforms(60, 120, bounces, aa, shadow)
-
-
-def images(r):
-    return r.read_rgba8(), r.read_rgba32f()
-
-
-_ab = {}
-
-
-def plain_ab(rm, u, W, H, scene=None, key=None):
-    """(A, B): the AA-off and AA-on frames of u, each (rgba8, rgba32f); kept per key."""
-    if key is None or key not in _ab:
-        with rm.Renderer(W, H, outputs=BOTH) as r:
-            if scene is not None:
-                r.set_scene(scene)
-            r.dispatch(with_aa(u, False))
-            a = images(r)
-            r.dispatch(with_aa(u, True))
-            b = images(r)
-        for x in a + b:
-            x.setflags(write=False)
-        if key is None:
-            return a, b
-        _ab[key] = (a, b)
-    return _ab[key]
-
-
-def expect(M, A, B):
-    m = M.astype(bool)[..., None]
-    return np.where(m, B[0], A[0]), np.where(m, B[1].view(np.uint32), A[1].view(np.uint32))
-
-
-def check_frame(r, M_want, A, B, what):
-    """The context's image and mask after an adaptive dispatch, against the definition."""
-    M = r.read_aa_mask()
-    assert M.dtype == np.uint8 and M.shape == M_want.shape
-    np.testing.assert_array_equal(M, M_want, err_msg=f"{what}: mask")
-    c8, c32 = images(r)
-    w8, w32 = expect(M_want, A, B)
-    assert c8.tobytes() == w8.tobytes(), f"{what}: rgba8, {int((c8 != w8).any(-1).sum())} pixels differ"
-    np.testing.assert_array_equal(c32.view(np.uint32), w32, err_msg=f"{what}: rgba32f")
-    assert r.aa_refined() == int(M_want.sum()), what
-    return M, c8, c32
 
 
 def check_adaptive(rm, r, u, thr, A, B, what):
@@ -88,7 +38,7 @@ def check_adaptive(rm, r, u, thr, A, B, what):
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_adaptive_equals_definition(rm, gpu, W, H, bounces):
     u = main_u(rm, bounces)
-    A, B = plain_ab(rm, u, W, H, key=(W, H, bounces, 0))
+    A, B = ab(refs(rm, W, H, bounces))
     with rm.Renderer(W, H, outputs=BOTH) as r:
         for thr in (0, 16, 255):
             M, c8, _ = check_adaptive(rm, r, u, thr, A, B, f"{W}x{H} b{bounces} thr{thr}")
@@ -110,22 +60,22 @@ def test_adaptive_equals_definition(rm, gpu, W, H, bounces):
 @pytest.mark.parametrize("shadow", [0, 1])
 def test_both_shadow_modes(rm, gpu, shadow):
     u = main_u(rm, 1, shadow)
-    A, B = plain_ab(rm, u, W0, H0, key=(W0, H0, 1, shadow))
+    A, B = ab(refs(rm, W0, H0, 1, shadow))
     with rm.Renderer(W0, H0, outputs=BOTH) as r:
         check_adaptive(rm, r, u, 16, A, B, f"shadow {shadow}")
     if shadow:
-        assert A[0].tobytes() != plain_ab(rm, main_u(rm, 1, 0), W0, H0, key=(W0, H0, 1, 0))[0][0].tobytes()
+        assert A[0].tobytes() != ab(refs(rm, W0, H0))[0][0].tobytes()
 
 
 @pytest.mark.parametrize("thr", [0, 16])
 def test_rgba32f_only_context(rm, gpu, thr):
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W0, H0, key=(W0, H0, 1, 0))
+    A, B = ab(refs(rm, W0, H0))
     with rm.Renderer(W0, H0, outputs=rm.RM_OUT_RGBA32F) as r:
         r.dispatch_adaptive(u, thr)
         M = r.read_aa_mask()
         np.testing.assert_array_equal(M, flag_mask(A[0], thr))
-        np.testing.assert_array_equal(r.read_rgba32f().view(np.uint32), expect(M, A, B)[1])
+        np.testing.assert_array_equal(r.read_rgba32f().view(np.uint32), expected(M, A, B)[1])
         assert r.aa_refined() == int(M.sum())
 
 
@@ -146,29 +96,12 @@ def test_against_the_oracle(rm, oracle, gpu, W, H):
 
 
 # ---- 3. caller masks, host and device -----------------------------------------------------------
-def caller_masks(W, H):
-    g = np.random.default_rng(20261019)
-    rnd = (g.random((H, W)) < 0.5).astype(np.uint8)
-    if rnd.sum() % 16 == 0:
-        rnd[0, 0] ^= 1
-    yy, xx = np.mgrid[0:H, 0:W]
-    corners = np.zeros((H, W), np.uint8)
-    corners[[0, 0, -1, -1], [0, -1, 0, -1]] = 1
-    one = np.zeros((H, W), np.uint8)
-    one[H // 2, W // 3] = 1
-    values = rnd.copy()  # any non-zero byte flags its pixel
-    values[rnd == 1] = np.where(g.random(int(rnd.sum())) < 0.5, 2, 255).astype(np.uint8)
-    return {"ones": np.ones((H, W), np.uint8), "zeros": np.zeros((H, W), np.uint8),
-            "checker": ((xx + yy) & 1).astype(np.uint8), "corners": corners, "one": one, "random": rnd,
-            "values": values}
-
-
 @pytest.mark.parametrize("where", ["host", "device"])
 def test_caller_masks(rm, gpu, where):
     import torch
     W, H = W0, H0
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W, H, key=(W, H, 1, 0))
+    A, B = ab(refs(rm, W, H))
     masks = caller_masks(W, H)
     assert masks["random"].sum() % 16 != 0 and set(np.unique(masks["values"])) == {0, 2, 255}
     with rm.Renderer(W, H, outputs=BOTH) as r:
@@ -210,7 +143,7 @@ def test_caller_masks(rm, gpu, where):
 def test_stride_loop(rm, gpu, monkeypatch):
     W, H = W0, H0
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W, H, key=(W, H, 1, 0))
+    A, B = ab(refs(rm, W, H))
     masks = caller_masks(W, H)
     monkeypatch.setenv("RM_AA_REFINE_WAVES", "3")  # 8710 pixels: 545 groups over 3 waves
     with rm.Renderer(W, H, outputs=BOTH) as r:
@@ -238,13 +171,10 @@ def test_default_scene_table_equals_builtin(rm, gpu):
                                               ("floor0", True)],
                          ids=["random0", "random1", "floor0", "floor0-specialised"])
 def test_tables(rm, gpu, which, specialize):
-    scene = floor_last_scene(rm, 0) if which == "floor0" else random_scene(rm, int(which[-1]))
+    scene = scene_of(rm, which)
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W0, H0, scene=scene, key=(W0, H0, which))
-    with rm.Renderer(W0, H0, outputs=BOTH) as r:
-        if specialize:
-            r.specialize_scene(True)
-        r.set_scene(scene)
+    A, B = ab(refs(rm, W0, H0, name=which))
+    with renderer(rm, W0, H0, scene, specialize=specialize) as r:
         check_adaptive(rm, r, u, 16, A, B, which)
         r.dispatch_refine(np.ones((H0, W0), np.uint8), u)
         check_frame(r, np.ones((H0, W0), np.uint8), A, B, f"{which} all ones")
@@ -253,14 +183,11 @@ def test_tables(rm, gpu, which, specialize):
 # ---- 6. uniforms off the sweep ------------------------------------------------------------------------
 @pytest.mark.parametrize("i", range(5), ids=[f"case{i}" for i in range(4)] + ["nan_camera"])
 def test_off_sweep_uniforms(rm, gpu, i):
-    import test_gpu_fuzz_uniforms as fz
-    u = fz._uniforms(rm, fz.CASES[i if i < 4 else 0])
-    if i == 4:
-        u.camera.pos[0] = float("nan")  # one non-finite camera
-    assert (fz.W, fz.H) == (67, 41)
+    u, (W, H) = off_sweep_uniforms(rm, i if i < 4 else 16)  # 16: one non-finite camera
+    assert (W, H) == (67, 41)
     with np.errstate(all="ignore"):
-        A, B = plain_ab(rm, u, fz.W, fz.H)
-        with rm.Renderer(fz.W, fz.H, outputs=BOTH) as r:
+        A, B = ab(refs(rm, W, H, u=u))
+        with rm.Renderer(W, H, outputs=BOTH) as r:
             check_adaptive(rm, r, u, 8, A, B, f"case {i}")
 
 
@@ -268,8 +195,8 @@ def test_off_sweep_uniforms(rm, gpu, i):
 def test_not_sticky_and_reusable(rm, gpu):
     W, H = W0, H0
     u, u2 = main_u(rm, 1, aa=True), rm.sweep_uniforms(20, 120, 2, False, 0)
-    A, B = plain_ab(rm, u, W, H, key=(W, H, 1, 0))
-    A2, _ = plain_ab(rm, u2, W, H, key=(W, H, "u2"))
+    A, B = ab(refs(rm, W, H))
+    A2, _ = ab(refs(rm, W, H, u=u2))
     masks = caller_masks(W, H)
     with rm.Renderer(W, H, outputs=BOTH) as r:
         r.enable_timing(True)
@@ -303,9 +230,9 @@ def test_stream_interop(rm, gpu):
     import torch
     W, H = W0, H0
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W, H, key=(W, H, 1, 0))
+    A, B = ab(refs(rm, W, H))
     m = caller_masks(W, H)["random"]
-    want8 = expect(m, A, B)[0]
+    want8 = expected(m, A, B)[0]
     with rm.Renderer(W, H, outputs=BOTH) as r:
         dev = torch.device("cuda", r.device)
         s, s2 = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
@@ -329,7 +256,7 @@ def test_stream_interop(rm, gpu):
                 with torch.cuda.stream(s2):
                     again = out.clone()
                 s2.synchronize()
-                assert again.cpu().numpy().tobytes() == expect(flag_mask(A[0], 16), A, B)[0].tobytes()
+                assert again.cpu().numpy().tobytes() == expected(flag_mask(A[0], 16), A, B)[0].tobytes()
             np.testing.assert_array_equal(r.read_aa_mask(), flag_mask(A[0], 16))
         finally:
             r.synchronize()
@@ -338,24 +265,6 @@ def test_stream_interop(rm, gpu):
 
 
 # ---- 9. refusals -------------------------------------------------------------------------------------------
-CALLS = ("rm_dispatch_adaptive", "rm_dispatch_refine", "rm_dispatch_refine_device")
-
-
-def _call(rm, r, name, mask, dev_ptr):
-    lib = rm.lib()
-    if name == "rm_dispatch_adaptive":
-        return lib.rm_dispatch_adaptive(r.handle, 16)
-    if name == "rm_dispatch_refine":
-        return lib.rm_dispatch_refine(r.handle, mask.ctypes.data, 0)
-    return lib.rm_dispatch_refine_device(r.handle, dev_ptr, 0)
-
-
-def _refused(rm, r, code, mask, dev_ptr):
-    for name in CALLS:
-        assert _call(rm, r, name, mask, dev_ptr) == code, name
-        assert name in rm.lib().rm_last_error(r.handle).decode(), name
-
-
 @pytest.mark.parametrize("kind", ["counters", "nshards", "gbuffer", "graph", "ngpus", "communicator"])
 def test_refused_contexts(rm, gpu, kind):
     import torch
@@ -378,7 +287,7 @@ def test_refused_contexts(rm, gpu, kind):
         if kind == "graph":
             r.graph_enable(True)
         r.set_uniforms(u)
-        _refused(rm, r, rm.RM_ERR_STATE, mask, dev.data_ptr())
+        refused(rm, r, rm.RM_ERR_STATE, None, None, mask, dev.data_ptr(), calls=ADAPTIVE_CALLS)
         # the context renders correctly afterwards
         r.dispatch(u)
         img = r.read_rgba8()
@@ -396,7 +305,7 @@ def test_refused_arguments_and_order(rm, gpu):
     W, H = 64, 48
     lib = rm.lib()
     u = main_u(rm)
-    A, B = plain_ab(rm, u, W, H)
+    A, B = ab(refs(rm, W, H))
     mask = np.ones((H, W), np.uint8)
     with rm.Renderer(W, H, outputs=BOTH) as r:
         dev = torch.ones((H, W), dtype=torch.uint8, device=f"cuda:{r.device}")

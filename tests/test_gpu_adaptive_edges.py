@@ -1,8 +1,9 @@
 """Geometry-edge adaptive supersampling on the GPU (rm_dispatch_adaptive_edges).
 
 Throughout, A is rm_dispatch with AA off and B rm_dispatch with AA on, on a plain context
-with both colour outputs, and G is the AA-off rm_dispatch G-buffer on a G-buffer context.  The
-definition: the mask M is the flagging rule (tests/adaptive_edges_model.py) applied to G and
+with both colour outputs, and G is the AA-off rm_dispatch G-buffer on a G-buffer context
+(tests/frames.py refs).  The definition (tests/adaptive_checks.py check_frame): the mask M is
+the flagging rule (tests/adaptive_edges_model.py) applied to G and
 A's RGBA8 image, exactly; the image is where(M, B, A), byte for byte in RGBA8 and bit for bit
 in RGBA32F; rm_read_gbuffer is G, bit for bit; rm_aa_refined is M.sum().
 
@@ -15,83 +16,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from adaptive_edges_model import ALBEDO, COLOR, DEPTH, ID, NORMAL, edge_mask
+from adaptive_checks import DEFAULTS, check_frame, criteria
+from adaptive_edges_model import ALBEDO, BITS, COLOR, COUNTS, DEPTH, ID, NORMAL, edge_mask
 from adaptive_model import flag_mask
-from test_adaptive_edges_model import BITS, COUNTS
-from test_gpu_scene import floor_last_scene, random_scene
+from frames import ALL, BOTH, refs, renderer
+from scenes import scene_of
+from uniforms import main_u, off_sweep_uniforms, with_aa
 
 pytestmark = pytest.mark.gpu
 
 W0, H0 = 130, 67
 SHAPES = [(130, 67), (37, 23), (9, 5), (8, 8), (1, 1)]
-BOTH, ALL = 3, 7  # RM_OUT_RGBA8 | RM_OUT_RGBA32F, | RM_OUT_GBUFFER
 GEOMETRY = ID | DEPTH | NORMAL | ALBEDO
 COMBOS = [COLOR, ID, DEPTH, NORMAL, ALBEDO, ID | DEPTH | NORMAL, GEOMETRY | COLOR]
-DEFAULTS = dict(color_threshold=8, depth_rel=0.05, normal_cos=0.9)
-
-
-def with_aa(u, aa):
-    v = type(u).from_buffer_copy(u)
-    v.AA = 1 if aa else 0
-    return v
-
-
-def main_u(rm, bounces=1):
-    return rm.sweep_uniforms(60, 120, bounces, False, 0)
-
-
-def images(r):
-    return r.read_rgba8(), r.read_rgba32f()
-
-
-_refs = {}
-
-
-def refs(rm, u, W, H, scene=None, key=None):
-    """A, B (each (rgba8, rgba32f)) from a plain context; G and the AA-on G-buffer from a
-    G-buffer context.  Rendered once per key and left unchanged."""
-    if key is None or key not in _refs:
-        with rm.Renderer(W, H, outputs=BOTH) as r:
-            if scene is not None:
-                r.set_scene(scene)
-            r.dispatch(with_aa(u, False))
-            a = images(r)
-            r.dispatch(with_aa(u, True))
-            b = images(r)
-        with rm.Renderer(W, H, outputs=ALL) as r:
-            if scene is not None:
-                r.set_scene(scene)
-            r.dispatch(with_aa(u, False))
-            g = r.read_gbuffer()
-            r.dispatch(with_aa(u, True))
-            g_aa = r.read_gbuffer()
-        for x in a + b + (g, g_aa):
-            x.setflags(write=False)
-        ref = {"A": a, "B": b, "G": g, "G_aa": g_aa}
-        if key is None:
-            return ref
-        _refs[key] = ref
-    return _refs[key]
-
-
-def check_frame(r, M_want, ref, what):
-    """The context after an adaptive dispatch, against the definition."""
-    A, B = ref["A"], ref["B"]
-    M = r.read_aa_mask()
-    assert M.dtype == np.uint8 and M.shape == M_want.shape
-    np.testing.assert_array_equal(M, M_want, err_msg=f"{what}: mask")
-    m = M_want.astype(bool)[..., None]
-    if r.outputs & 1:
-        c8, w8 = r.read_rgba8(), np.where(m, B[0], A[0])
-        assert c8.tobytes() == w8.tobytes(), f"{what}: rgba8, {int((c8 != w8).any(-1).sum())} pixels differ"
-    if r.outputs & 2:
-        np.testing.assert_array_equal(r.read_rgba32f().view(np.uint32),
-                                      np.where(m, B[1].view(np.uint32), A[1].view(np.uint32)),
-                                      err_msg=f"{what}: rgba32f")
-    if r.outputs & 4:
-        assert r.read_gbuffer().tobytes() == ref["G"].tobytes(), f"{what}: the G-buffer is pass 1's"
-    assert r.aa_refined() == int(M_want.sum()), what
-    return M
 
 
 def check_edges(r, u, edges, ref, what, **kw):
@@ -99,7 +36,7 @@ def check_edges(r, u, edges, ref, what, **kw):
     r.dispatch_adaptive_edges(u, edges, **par)
     with np.errstate(all="ignore"):
         want = edge_mask(ref["G"], ref["A"][0], edges, **par)
-    return check_frame(r, want, ref, f"{what} edges {edges}")
+    return check_frame(r, want, ref["A"], ref["B"], f"{what} edges {edges}", ref["G"])[0]
 
 
 # ---- 1. the definition ----------------------------------------------------------------------------
@@ -107,7 +44,7 @@ def check_edges(r, u, edges, ref, what, **kw):
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_edges_equal_definition(rm, gpu, W, H, bounces):
     u = main_u(rm, bounces)
-    ref = refs(rm, u, W, H, key=(W, H, bounces))
+    ref = refs(rm, W, H, bounces)
     with rm.Renderer(W, H, outputs=ALL) as r:
         for edges in COMBOS:
             M = check_edges(r, u, edges, ref, f"{W}x{H} b{bounces}")
@@ -125,14 +62,14 @@ def test_edges_equal_definition(rm, gpu, W, H, bounces):
         # u.AA is ignored, and the uniforms stay as they are
         r.dispatch_adaptive_edges(with_aa(u, True), ID | DEPTH | NORMAL)
         assert r.get_uniforms().AA == 1
-        check_frame(r, edge_mask(ref["G"], None, ID | DEPTH | NORMAL, **DEFAULTS), ref, "u.AA = 1")
+        check_frame(r, edge_mask(ref["G"], None, ID | DEPTH | NORMAL, **DEFAULTS), ref["A"], ref["B"], "u.AA = 1", ref["G"])
 
 
 @pytest.mark.parametrize("outputs", [1 | 4, 2 | 4], ids=["rgba8", "rgba32f"])
 def test_one_colour_output(rm, gpu, outputs):
     """COLOR reads the RGBA8 image, or quantises the RGBA32F one."""
     u = main_u(rm)
-    ref = refs(rm, u, W0, H0, key=(W0, H0, 1))
+    ref = refs(rm, W0, H0)
     with rm.Renderer(W0, H0, outputs=outputs) as r:
         for edges in (COLOR, GEOMETRY | COLOR):
             check_edges(r, u, edges, ref, f"outputs {outputs}")
@@ -142,7 +79,7 @@ def test_one_colour_output(rm, gpu, outputs):
 def test_plain_form_gives_the_same_frame(rm, gpu, monkeypatch, W, H):
     """RM_AA_EDGES_NAIVE: the classifier with four pair tests per lane, kept for measurement."""
     u = main_u(rm, 2)
-    ref = refs(rm, u, W, H, key=(W, H, 2))
+    ref = refs(rm, W, H, 2)
     with rm.Renderer(W, H, outputs=ALL) as r:
         monkeypatch.setenv("RM_AA_EDGES_NAIVE", "1")  # read by every call
         for edges in COMBOS:
@@ -155,7 +92,7 @@ def test_plain_form_gives_the_same_frame(rm, gpu, monkeypatch, W, H):
 @pytest.mark.parametrize("outputs", [BOTH, ALL], ids=["plain", "gbuffer"])
 def test_color_alone_is_dispatch_adaptive(rm, gpu, outputs):
     u = main_u(rm)
-    ref = refs(rm, u, W0, H0, key=(W0, H0, 1))
+    ref = refs(rm, W0, H0)
     with rm.Renderer(W0, H0, outputs=BOTH) as p, rm.Renderer(W0, H0, outputs=outputs) as r:
         for thr in (0, 8, 255):
             p.dispatch_adaptive(u, thr)
@@ -164,20 +101,17 @@ def test_color_alone_is_dispatch_adaptive(rm, gpu, outputs):
             assert r.read_rgba8().tobytes() == p.read_rgba8().tobytes()
             assert r.read_rgba32f().tobytes() == p.read_rgba32f().tobytes()
             assert r.aa_refined() == p.aa_refined()
-            check_frame(r, flag_mask(ref["A"][0], thr), ref, f"thr {thr}")
+            check_frame(r, flag_mask(ref["A"][0], thr), ref["A"], ref["B"], f"thr {thr}", ref["G"])
 
 
 # ---- 3. tables ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("specialize", [False, True], ids=["generic", "specialised"])
 @pytest.mark.parametrize("which", ["random0", "floor0"])
 def test_tables(rm, gpu, which, specialize):
-    scene = floor_last_scene(rm, 0) if which == "floor0" else random_scene(rm, 0)
+    scene = scene_of(rm, which)
     u = main_u(rm)
-    ref = refs(rm, u, W0, H0, scene=scene, key=(W0, H0, which))
-    with rm.Renderer(W0, H0, outputs=ALL) as r:
-        if specialize:
-            r.specialize_scene(True)
-        r.set_scene(scene)
+    ref = refs(rm, W0, H0, name=which)
+    with renderer(rm, W0, H0, scene, ALL, specialize) as r:
         for edges in COMBOS:
             check_edges(r, u, edges, ref, which)
 
@@ -187,7 +121,7 @@ def test_caller_owned_gbuffer(rm, gpu):
     import torch
     W, H = 37, 23
     u, u2 = main_u(rm), rm.sweep_uniforms(20, 120, 1, False, 0)
-    ref = refs(rm, u, W, H, key=(W, H, 1))
+    ref = refs(rm, W, H)
     edges = ID | DEPTH | NORMAL
     want = edge_mask(ref["G"], None, edges, **DEFAULTS)
     with rm.Renderer(W, H, outputs=ALL) as r:
@@ -210,7 +144,7 @@ def test_caller_owned_gbuffer(rm, gpu):
             assert gotg[:H * W * 8].tobytes() == ref["G"].tobytes(), "the caller's buffer holds pass 1's records"
             assert (gotg[H * W * 8:] == np.float32(-7.25)).all(), "the sentinel after the last record"
             assert got8.tobytes() == np.where(want.astype(bool)[..., None], ref["B"][0], ref["A"][0]).tobytes()
-            check_frame(r, want, ref, "caller-owned")  # the mask is the caller's buffer's, not the stale one's
+            check_frame(r, want, ref["A"], ref["B"], "caller-owned", ref["G"])  # the caller's buffer's mask, not the stale one's
         finally:
             r.synchronize()
             r.set_output_gbuffer(None)
@@ -222,11 +156,10 @@ def test_caller_owned_gbuffer(rm, gpu):
 # ---- 5. uniforms off the sweep -----------------------------------------------------------------------------
 @pytest.mark.parametrize("i", [0, 1, 2, 3, 16], ids=[f"case{i}" for i in range(4)] + ["nan_camera"])
 def test_off_sweep_uniforms(rm, gpu, i):
-    from test_gpu_gbuffer import _fuzz_uniforms
-    u, (W, H) = _fuzz_uniforms(rm, i)
+    u, (W, H) = off_sweep_uniforms(rm, i)
     assert (W, H) == (67, 41)
     with np.errstate(all="ignore"):
-        ref = refs(rm, u, W, H)
+        ref = refs(rm, W, H, u=u)
         with rm.Renderer(W, H, outputs=ALL) as r:
             r.dispatch(with_aa(u, False))
             own = r.read_gbuffer()  # this context's own G
@@ -238,7 +171,7 @@ def test_off_sweep_uniforms(rm, gpu, i):
 # ---- 6. extremes ----------------------------------------------------------------------------------------------
 def test_extremes(rm, gpu):
     u = main_u(rm)
-    ref = refs(rm, u, W0, H0, key=(W0, H0, 1))
+    ref = refs(rm, W0, H0)
     with rm.Renderer(W0, H0, outputs=ALL) as r:
         M0 = check_edges(r, u, DEPTH, ref, "depth_rel 0", depth_rel=0.0)
         assert M0.sum() >= COUNTS[(W0, H0)]["DEPTH"]  # a wider net than depth_rel 0.05's
@@ -253,7 +186,7 @@ def test_extremes(rm, gpu):
 # ---- 7. nothing sticky ------------------------------------------------------------------------------------------
 def test_nothing_sticky(rm, gpu):
     u = main_u(rm)
-    ref = refs(rm, u, W0, H0, key=(W0, H0, 1))
+    ref = refs(rm, W0, H0)
     with rm.Renderer(W0, H0, outputs=ALL) as r:
         r.enable_timing(True)
         _, n0 = r.kernel_time_ms()
@@ -275,10 +208,6 @@ def test_nothing_sticky(rm, gpu):
 
 
 # ---- 8. refused contexts -----------------------------------------------------------------------------------------
-def criteria(rm, edges, color_threshold=8, depth_rel=0.05, normal_cos=0.9, size=20):
-    return rm.rm_aa_criteria(size, edges, color_threshold, depth_rel, normal_cos)
-
-
 @pytest.mark.parametrize("kind", ["no_gbuffer", "gbuffer_only", "counters", "nshards", "nshards_gbuffer", "graph"])
 def test_refused_contexts(rm, gpu, kind):
     W, H = 64, 48
@@ -324,7 +253,7 @@ def test_refused_arguments(rm, gpu):
     W, H = 37, 23
     lib = rm.lib()
     u = main_u(rm)
-    ref = refs(rm, u, W, H, key=(W, H, 1))
+    ref = refs(rm, W, H)
     nan = float("nan")
     bad = [("edges = 0", criteria(rm, 0), None),
            ("an unknown bit", criteria(rm, ID | 32), None),
@@ -359,7 +288,8 @@ def test_refused_arguments(rm, gpu):
                 good.update({k: v for k, v in par.items() if k in _read_under(accepted_with)})
                 assert lib.rm_dispatch_adaptive_edges(r.handle, C.byref(cr)) == rm.RM_OK, what
                 with np.errstate(all="ignore"):
-                    check_frame(r, edge_mask(ref["G"], ref["A"][0], accepted_with, **good), ref, f"{what}, bit clear")
+                    want = edge_mask(ref["G"], ref["A"][0], accepted_with, **good)
+                    check_frame(r, want, ref["A"], ref["B"], f"{what}, bit clear", ref["G"])
         # the mask's pointer and readers work on a G-buffer context
         assert r.aa_mask_ptr() != 0
         assert lib.rm_read_aa_mask(r.handle, out.ctypes.data, W - 1, 0) == rm.RM_ERR_INVALID

@@ -2,144 +2,37 @@
 rm_dispatch_refine_pattern / _device; include/rm_api.h RM_HAS_ADAPTIVE_PATTERN).
 
 The definition.  For a frame u, a scene and a pattern p, three references come from other
-calls of the same library: A, the AA-off rm_dispatch frame, and P, the rm_dispatch_pattern(p)
-frame, both on a plain context with both colour outputs (G-buffer contexts refuse
-rm_dispatch_pattern); G, the AA-off rm_dispatch G-buffer of a G-buffer context.  The expected
+calls of the same library (tests/frames.py refs): A, the AA-off rm_dispatch frame, and P, the
+rm_dispatch_pattern(p) frame, both on a plain context with both colour outputs (G-buffer contexts
+refuse rm_dispatch_pattern); G, the AA-off rm_dispatch G-buffer of a G-buffer context.  The expected
 mask M is tests/adaptive_edges_model.py's rule on G (and A's RGBA8 under COLOR), or the mask
 given.  Then the call's mask is M, rm_aa_refined is M.sum(), the frame is where(M, P, A) bit for
-bit in RGBA32F and byte for byte in RGBA8, and the G-buffer is G bit for bit.
+bit in RGBA32F and byte for byte in RGBA8, and the G-buffer is G bit for bit
+(tests/adaptive_checks.py check_frame).
 
-Frames are rm_sweep_uniforms(60, 120, ., 0, .) as in tests/test_gpu_adaptive_edges.py.  The
+Frames are rm_sweep_uniforms(60, 120, ., 0, .) (tests/uniforms.py main_u).  The
 shapes: 130 x 67 (several tiles, a partial last group), 37 x 23, 9 x 5, 8 x 8 and 1 x 1 (no
 neighbour, nothing flagged).  Every edges case at 9 x 5 and above asserts 0 < flagged < W H on
 the expected mask; tests/test_adaptive_pattern_abi.py holds the same condition against the
 oracle's G-buffer on the CPU for the frames and criteria used here.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import sample_pattern_model as SPM
-from adaptive_edges_model import COLOR, DEPTH, ID, NORMAL, edge_mask
+from adaptive_checks import DEFAULTS, E3, call, check_frame, criteria, edges_mask, expected, refused, some_mask
+from adaptive_checks import PATTERN_CALLS as CALLS
+from adaptive_edges_model import COLOR, DEPTH, ID, NORMAL
 from adaptive_model import flag_mask
-from test_gpu_pattern import equals_model, model, random_patterns
-from test_gpu_scene import random_scene
+from frames import ALL, BOTH, images, pattern_frame, refs, renderer
+from patterns import equals_model, model
+from patterns import refine_patterns as patterns
+from scenes import scene_of
+from uniforms import main_u
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(130, 67), (37, 23), (9, 5), (8, 8), (1, 1)]
-BOTH, ALL = 3, 7  # RM_OUT_RGBA8 | RM_OUT_RGBA32F, | RM_OUT_GBUFFER
-E3 = ID | DEPTH | NORMAL  # rm_aa_criteria_init's
-DEFAULTS = dict(color_threshold=8, depth_rel=0.05, normal_cos=0.9)
 SCENES = ["builtin", "default-table", "random-table"]
-
-
-def scene_of(rm, name):
-    return {"builtin": None, "default-table": rm.default_scene(), "random-table": random_scene(rm, 0)}[name]
-
-
-def main_u(rm, bounces=1, shadow=0, aa=False):
-    return rm.sweep_uniforms(60, 120, bounces, aa, shadow)
-
-
-def patterns(rm):
-    """The ten patterns of the issue: rounds 1 (GRID2, RGSS, REFERENCE, abs2), 2 (abs7: 4 + 3),
-    3 (GRID3: 4 + 4 + 1), 4 (GRID4, cum16) and the two one-sample kernels' (jitter1, centre)."""
-    rng = np.random.default_rng(22)
-    a2 = rng.uniform(-1.5, 1.5, (2, 2)).astype(np.float32)
-    out = {"grid2": rm.sample_pattern(rm.RM_PATTERN_GRID2), "rgss": rm.sample_pattern(rm.RM_PATTERN_RGSS),
-           "grid3": rm.sample_pattern(rm.RM_PATTERN_GRID3), "grid4": rm.sample_pattern(rm.RM_PATTERN_GRID4),
-           "reference": rm.sample_pattern(rm.RM_PATTERN_REFERENCE), "abs2": rm.custom_pattern(a2[0], a2[1])}
-    out.update(random_patterns(rm))  # abs7, cum16, jitter1
-    out["centre"] = rm.custom_pattern([0.0], [0.0])
-    return out
-
-
-def images(r):
-    return r.read_rgba8(), r.read_rgba32f()
-
-
-def renderer(rm, W, H, scene=None, outputs=BOTH, specialize=False, **kw):
-    r = rm.Renderer(W, H, outputs=outputs, **kw)
-    if specialize:
-        r.specialize_scene(True)
-    if scene is not None:
-        r.set_scene(scene)
-    return r
-
-
-_refs, _pats = {}, {}
-
-
-def refs(rm, W, H, bounces=1, shadow=0, name="builtin"):
-    """A = (rgba8, rgba32f) of the AA-off frame on a plain context and G, the AA-off G-buffer of
-    a G-buffer context.  Rendered once per key and left unchanged."""
-    key = (name, W, H, bounces, shadow)
-    if key not in _refs:
-        u = main_u(rm, bounces, shadow)
-        with renderer(rm, W, H, scene_of(rm, name)) as r:
-            r.dispatch(u)
-            a = images(r)
-        with renderer(rm, W, H, scene_of(rm, name), outputs=ALL) as r:
-            r.dispatch(u)
-            g = r.read_gbuffer()
-        for x in a + (g,):
-            x.setflags(write=False)
-        _refs[key] = {"A": a, "G": g}
-    return _refs[key]
-
-
-def pattern_frame(rm, W, H, p, pname, bounces=1, shadow=0, name="builtin"):
-    """P = (rgba8, rgba32f): rm_dispatch_pattern(p) on a plain context, once per key."""
-    key = (name, W, H, bounces, shadow, pname)
-    if key not in _pats:
-        with renderer(rm, W, H, scene_of(rm, name)) as r:
-            r.dispatch_pattern(main_u(rm, bounces, shadow), p)
-            _pats[key] = images(r)
-        for x in _pats[key]:
-            x.setflags(write=False)
-    return _pats[key]
-
-
-def expected(M, A, P):
-    m = np.asarray(M).astype(bool)[..., None]
-    return np.where(m, P[0], A[0]), np.where(m, P[1].view(np.uint32), A[1].view(np.uint32))
-
-
-def check_frame(r, M_want, ref, P, what):
-    """The context after a pattern refinement, against the definition."""
-    M = r.read_aa_mask()
-    assert M.dtype == np.uint8 and M.shape == M_want.shape
-    np.testing.assert_array_equal(M, M_want, err_msg=f"{what}: mask")
-    assert r.aa_refined() == int(M_want.sum()), what
-    w8, w32 = expected(M_want, ref["A"], P)
-    if r.outputs & 2:
-        np.testing.assert_array_equal(r.read_rgba32f().view(np.uint32), w32, err_msg=f"{what}: rgba32f")
-    if r.outputs & 1:
-        c8 = r.read_rgba8()
-        assert c8.tobytes() == w8.tobytes(), f"{what}: rgba8, {int((c8 != w8).any(-1).sum())} pixels differ"
-    if r.outputs & 4:
-        assert r.read_gbuffer().tobytes() == ref["G"].tobytes(), f"{what}: the G-buffer is pass 1's"
-
-
-def edges_mask(ref, W, H, edges=E3, **kw):
-    """The expected mask of an edges case, never empty and never full at 9 x 5 and above."""
-    with np.errstate(all="ignore"):
-        M = edge_mask(ref["G"], ref["A"][0], edges, **dict(DEFAULTS, **kw))
-    if (W, H) == (1, 1):
-        assert not M.any()
-    else:
-        assert 0 < int(M.sum()) < W * H, (W, H, edges, int(M.sum()))
-    return M
-
-
-def some_mask(W, H, k, seed=5):
-    """k flagged pixels of a W x H frame, as bytes of several non-zero values."""
-    rng = np.random.default_rng(seed + k)
-    m = np.zeros(W * H, np.uint8)
-    m[rng.choice(W * H, k, replace=False)] = rng.choice([1, 7, 128, 255], k)
-    return m.reshape(H, W)
 
 
 # ---- 1. every pattern against the definition -----------------------------------------------------
@@ -155,7 +48,7 @@ def test_patterns_equal_definition(rm, gpu, W, H, bounces, shadow):
         for pname, p in patterns(rm).items():
             P = pattern_frame(rm, W, H, p, pname, bounces, shadow)
             r.dispatch_adaptive_pattern(u, None, p)
-            check_frame(r, M, ref, P, f"{W}x{H} b{bounces} s{shadow} {pname}")
+            check_frame(r, M, ref["A"], P, f"{W}x{H} b{bounces} s{shadow} {pname}", ref["G"])
         if (W, H) == (130, 67):  # the frame is neither of its two sources
             P = pattern_frame(rm, W, H, rm.sample_pattern(rm.RM_PATTERN_GRID4), "grid4", bounces, shadow)
             r.dispatch_adaptive_pattern(u, None, rm.RM_PATTERN_GRID4)
@@ -165,8 +58,8 @@ def test_patterns_equal_definition(rm, gpu, W, H, bounces, shadow):
         u_on = main_u(rm, bounces, shadow, True)
         r.dispatch_adaptive_pattern(u_on, None, rm.RM_PATTERN_GRID3)
         assert bytes(r.get_uniforms()) == bytes(u_on)
-        check_frame(r, M, ref, pattern_frame(rm, W, H, rm.sample_pattern(rm.RM_PATTERN_GRID3), "grid3", bounces, shadow),
-                    "u.AA = 1")
+        check_frame(r, M, ref["A"], pattern_frame(rm, W, H, rm.sample_pattern(rm.RM_PATTERN_GRID3), "grid3", bounces, shadow),
+                    "u.AA = 1", ref["G"])
 
 
 # ---- 2. against the rule directly: a fault shared with k_pattern cannot hide -----------------------
@@ -174,7 +67,7 @@ def test_patterns_equal_definition(rm, gpu, W, H, bounces, shadow):
 @pytest.mark.parametrize("name", ["builtin", "random-table"])
 def test_flagged_pixels_equal_the_rule(rm, oracle, gpu, name, pname):
     """The flagged pixels against tests/sample_pattern_model.py over SHADE traces of the same
-    context (the model of tests/test_gpu_pattern.py), the others against A."""
+    context (tests/patterns.py model), the others against A."""
     W, H = 37, 23
     u = main_u(rm, 2)
     ref = refs(rm, W, H, 2, 0, name)
@@ -236,7 +129,7 @@ def test_all_ones_mask_is_the_pattern_frame(rm, gpu, W, H):
             assert r.aa_refined() == W * H
             assert r.read_rgba8().tobytes() == P[0].tobytes(), pname
             assert r.read_rgba32f().tobytes() == P[1].tobytes(), pname
-            check_frame(r, np.ones((H, W), np.uint8), ref, P, f"{W}x{H} ones {pname}")
+            check_frame(r, np.ones((H, W), np.uint8), ref["A"], P, f"{W}x{H} ones {pname}", ref["G"])
 
 
 def test_nothing_flagged_is_the_plain_frame(rm, gpu):
@@ -249,17 +142,17 @@ def test_nothing_flagged_is_the_plain_frame(rm, gpu):
     with renderer(rm, W, H) as r:
         for p in (g4, patterns(rm)["jitter1"]):
             r.dispatch_refine_pattern(zero, p, u)
-            check_frame(r, zero, ref, ref["A"], "zero mask")
+            check_frame(r, zero, ref["A"], ref["A"], "zero mask", ref["G"])
             r.dispatch_adaptive_pattern(u, dict(edges=COLOR, color_threshold=255), p)
-            check_frame(r, zero, ref, ref["A"], "threshold 255")
+            check_frame(r, zero, ref["A"], ref["A"], "threshold 255", ref["G"])
     centre = patterns(rm)["centre"]
     with renderer(rm, W, H, outputs=ALL) as r:
         M = edges_mask(ref, W, H)
         r.dispatch_adaptive_pattern(u, None, centre)
-        check_frame(r, M, ref, ref["A"], "centre, edges")
+        check_frame(r, M, ref["A"], ref["A"], "centre, edges", ref["G"])
         ones = np.ones((H, W), np.uint8)
         r.dispatch_refine_pattern(ones, centre)
-        check_frame(r, ones, ref, ref["A"], "centre, all ones")
+        check_frame(r, ones, ref["A"], ref["A"], "centre, all ones", ref["G"])
 
 
 @pytest.mark.parametrize("pname", ["jitter1", "grid3"])
@@ -275,7 +168,7 @@ def test_group_ends(rm, gpu, pname):
         for k in (1, 15, 16, 17, 63, 64, 65):
             m = some_mask(W, H, k)
             r.dispatch_refine_pattern(m, p, u)
-            check_frame(r, (m != 0).astype(np.uint8), ref, P, f"{pname} {k} flagged")
+            check_frame(r, (m != 0).astype(np.uint8), ref["A"], P, f"{pname} {k} flagged", ref["G"])
 
 
 # ---- 4. one wave strides over every group: the LDS sum is reused between groups -------------------
@@ -291,10 +184,10 @@ def test_one_wave_walks_every_group(rm, gpu, monkeypatch, pname):
         monkeypatch.delenv("RM_AA_REFINE_WAVES")  # read at rm_create
         ones = np.ones((H, W), np.uint8)
         r.dispatch_refine_pattern(ones, p, u)
-        check_frame(r, ones, ref, P, f"one wave, {pname}")
+        check_frame(r, ones, ref["A"], P, f"one wave, {pname}", ref["G"])
         m = some_mask(W, H, 333)
         r.dispatch_refine_pattern(m, p)
-        check_frame(r, (m != 0).astype(np.uint8), ref, P, f"one wave, {pname}, 333 flagged")
+        check_frame(r, (m != 0).astype(np.uint8), ref["A"], P, f"one wave, {pname}, 333 flagged", ref["G"])
 
 
 # ---- 5. the sum follows the pattern's order ------------------------------------------------------------
@@ -335,12 +228,12 @@ def test_tables(rm, gpu, name, specialize):
         for pname in ("grid3", "grid4", "reference", "jitter1"):
             p = patterns(rm)[pname]
             r.dispatch_adaptive_pattern(u, None, p)
-            check_frame(r, M, ref, pattern_frame(rm, W, H, p, pname, 1, 0, name), f"{name} {pname}")
+            check_frame(r, M, ref["A"], pattern_frame(rm, W, H, p, pname, 1, 0, name), f"{name} {pname}", ref["G"])
         ones = np.ones((H, W), np.uint8)
         for pname in ("abs7", "jitter1"):
             p = patterns(rm)[pname]
             r.dispatch_refine_pattern(ones, p)
-            check_frame(r, ones, ref, pattern_frame(rm, W, H, p, pname, 1, 0, name), f"{name} ones {pname}")
+            check_frame(r, ones, ref["A"], pattern_frame(rm, W, H, p, pname, 1, 0, name), f"{name} ones {pname}", ref["G"])
     if name == "default-table":  # the default table is the built-in scene
         assert refs(rm, W, H, 1, 0)["G"].tobytes() == ref["G"].tobytes()
 
@@ -360,7 +253,7 @@ def test_outputs(rm, gpu, outputs):
             for pname in ("grid3", "jitter1"):
                 p = patterns(rm)[pname]
                 r.dispatch_adaptive_pattern(u, dict(DEFAULTS, edges=edges), p)
-                check_frame(r, M, ref, pattern_frame(rm, W, H, p, pname, 1, 0), f"outputs {outputs} edges {edges} {pname}")
+                check_frame(r, M, ref["A"], pattern_frame(rm, W, H, p, pname, 1, 0), f"outputs {outputs} edges {edges} {pname}", ref["G"])
     if outputs == 3:  # COLOR alone is rm_dispatch_adaptive's rule
         np.testing.assert_array_equal(M, flag_mask(ref["A"][0], 8))
 
@@ -378,17 +271,17 @@ def test_mask_calls_on_a_gbuffer_context(rm, gpu):
     want = (m != 0).astype(np.uint8)
     with renderer(rm, W, H, outputs=ALL) as r:
         r.dispatch_refine_pattern(m, pats["grid4"], u)  # row_pitch W + 5
-        check_frame(r, want, ref, pattern_frame(rm, W, H, pats["grid4"], "grid4", 1, 0), "host mask")
+        check_frame(r, want, ref["A"], pattern_frame(rm, W, H, pats["grid4"], "grid4", 1, 0), "host mask", ref["G"])
         ptr = r.aa_mask_ptr()
         for pname in ("grid3", "jitter1"):
             r.dispatch_refine_pattern(ptr, pats[pname], None, 0)  # its own normalised copy
-            check_frame(r, want, ref, pattern_frame(rm, W, H, pats[pname], pname, 1, 0), f"own mask {pname}")
+            check_frame(r, want, ref["A"], pattern_frame(rm, W, H, pats[pname], pname, 1, 0), f"own mask {pname}", ref["G"])
         assert r.aa_mask_ptr() == ptr
         # a G-buffer criterion of the caller's own: the floor's pixels, from the records just written
         own = (r.read_gbuffer()["id"] == 7).astype(np.uint8)
         assert 0 < own.sum() < W * H
         r.dispatch_refine_pattern(own, pats["grid3"])
-        check_frame(r, own, ref, pattern_frame(rm, W, H, pats["grid3"], "grid3", 1, 0), "own criterion")
+        check_frame(r, own, ref["A"], pattern_frame(rm, W, H, pats["grid3"], "grid3", 1, 0), "own criterion", ref["G"])
 
 
 def test_caller_owned_images_and_stream(rm, gpu):
@@ -417,7 +310,7 @@ def test_caller_owned_images_and_stream(rm, gpu):
             assert gotg[:H * W * 8].tobytes() == ref["G"].tobytes(), "the caller's buffer holds pass 1's records"
             assert (gotg[H * W * 8:] == np.float32(-7.25)).all(), "the sentinel after the last record"
             assert got8.tobytes() == expected(M, ref["A"], P)[0].tobytes()
-            check_frame(r, M, ref, P, "caller-owned")
+            check_frame(r, M, ref["A"], P, "caller-owned", ref["G"])
         finally:
             r.synchronize()
             r.set_output_gbuffer(None)
@@ -442,7 +335,7 @@ def test_nothing_sticky(rm, gpu):
         want_edges = images(fresh)
     with renderer(rm, W, H, outputs=ALL) as r:
         r.dispatch_adaptive_pattern(u_on, None, pats["grid4"])
-        check_frame(r, M, ref, pattern_frame(rm, W, H, pats["grid4"], "grid4", 1, 0), "first")
+        check_frame(r, M, ref["A"], pattern_frame(rm, W, H, pats["grid4"], "grid4", 1, 0), "first", ref["G"])
         assert bytes(r.get_uniforms()) == bytes(u_on)
         r.dispatch()  # the plain AA-on frame, as always, with the first sample's G-buffer
         assert images(r)[0].tobytes() == want_on[0].tobytes() and images(r)[1].tobytes() == want_on[1].tobytes()
@@ -452,7 +345,7 @@ def test_nothing_sticky(rm, gpu):
         assert images(r)[0].tobytes() == want_edges[0].tobytes() and images(r)[1].tobytes() == want_edges[1].tobytes()
         for pname in ("grid3", "jitter1", "grid4", "grid4", "abs7", "grid3"):  # patterns in turn
             r.dispatch_adaptive_pattern(None, None, pats[pname])
-            check_frame(r, M, ref, pattern_frame(rm, W, H, pats[pname], pname, 1, 0), f"in turn: {pname}")
+            check_frame(r, M, ref["A"], pattern_frame(rm, W, H, pats[pname], pname, 1, 0), f"in turn: {pname}", ref["G"])
         r.dispatch(u)
         assert r.read_rgba8().tobytes() == ref["A"][0].tobytes() and r.read_gbuffer().tobytes() == ref["G"].tobytes()
     # a plain context: rm_dispatch_pattern afterwards, and the table's cache shared by both kinds of call
@@ -464,11 +357,11 @@ def test_nothing_sticky(rm, gpu):
             r.dispatch_pattern(u, g2)
             assert r.read_rgba8().tobytes() == P2[0].tobytes() and r.read_rgba32f().tobytes() == P2[1].tobytes(), i
             r.dispatch_refine_pattern(m, g4)
-            check_frame(r, (m != 0).astype(np.uint8), ref, P4, f"alternating {i}")
+            check_frame(r, (m != 0).astype(np.uint8), ref["A"], P4, f"alternating {i}", ref["G"])
         r.dispatch_pattern(None, g4)  # the refinement's table, not uploaded again: the same frame
         assert r.read_rgba8().tobytes() == P4[0].tobytes() and r.read_rgba32f().tobytes() == P4[1].tobytes()
         r.dispatch_refine_pattern(m, g4)
-        check_frame(r, (m != 0).astype(np.uint8), ref, P4, "after rm_dispatch_pattern of the same pattern")
+        check_frame(r, (m != 0).astype(np.uint8), ref["A"], P4, "after rm_dispatch_pattern of the same pattern", ref["G"])
 
 
 # ---- 9. offsets far outside the pixel ---------------------------------------------------------------------------------
@@ -486,7 +379,7 @@ def test_sixteen_pixel_offsets(rm, oracle, gpu, name):
     p = rm.custom_pattern([16.0, -16.0, 16.0, -16.0], [16.0, 16.0, -16.0, -16.0])
     with renderer(rm, W, H, scene_of(rm, name), outputs=ALL) as r:
         r.dispatch_adaptive_pattern(u, None, p)
-        check_frame(r, M, ref, pattern_frame(rm, W, H, p, "pm16", 2, 0, name), f"{name} +-16")
+        check_frame(r, M, ref["A"], pattern_frame(rm, W, H, p, "pm16", 2, 0, name), f"{name} +-16", ref["G"])
         got = images(r)
         m8, m32 = model(rm, oracle, r, u, p)
     b = M.astype(bool)
@@ -514,33 +407,6 @@ def test_one_timed_launch_per_call(rm, gpu):
 
 
 # ---- 11. refusals -------------------------------------------------------------------------------------------------------
-CALLS = ("rm_dispatch_adaptive_pattern", "rm_dispatch_refine_pattern", "rm_dispatch_refine_pattern_device")
-
-
-def criteria(rm, edges, color_threshold=8, depth_rel=0.05, normal_cos=0.9, size=20):
-    return rm.rm_aa_criteria(size, edges, color_threshold, depth_rel, normal_cos)
-
-
-def call(rm, r, name, p, cr=None, mask=None, dev_ptr=0, pitch=0):
-    """The C call itself, its status returned."""
-    lib = rm.lib()
-    pp = C.byref(p) if p is not None else None
-    if name == "rm_dispatch_adaptive_pattern":
-        return lib.rm_dispatch_adaptive_pattern(r.handle, C.byref(cr) if cr is not None else None, pp)
-    if name == "rm_dispatch_refine_pattern":
-        return lib.rm_dispatch_refine_pattern(r.handle, mask.ctypes.data if mask is not None else None, pitch, pp)
-    return lib.rm_dispatch_refine_pattern_device(r.handle, dev_ptr or None, pitch, pp)
-
-
-def refused(rm, r, code, p, cr, mask, dev_ptr, word=None, pitch=0, calls=CALLS):
-    for name in calls:
-        assert call(rm, r, name, p, cr, mask, dev_ptr, pitch) == code, name
-        msg = rm.lib().rm_last_error(r.handle).decode()
-        assert msg.startswith(name + ": "), (name, msg)
-        if word:
-            assert word in msg, (name, msg)
-
-
 @pytest.mark.parametrize("kind", ["counters", "nshards", "graph", "ngpus", "gbuffer_only", "no_gbuffer"])
 def test_refused_contexts(rm, gpu, kind):
     import torch
@@ -614,7 +480,7 @@ def test_refused_patterns(rm, gpu):
             for name in CALLS:
                 assert call(rm, r, name, p, *args) == rm.RM_OK, (name, v)
             r.dispatch_adaptive_pattern(None, cr, p)
-            check_frame(r, M, ref, P, f"a bad offset at index n ({v})")
+            check_frame(r, M, ref["A"], P, f"a bad offset at index n ({v})", ref["G"])
         # the context's last frame is untouched by a refusal
         before = images(r)
         refused(rm, r, rm.RM_ERR_INVALID, None, *args)
@@ -645,8 +511,8 @@ def test_refused_criteria_and_masks(rm, gpu):
             refused(rm, r, rm.RM_ERR_INVALID, p, cr, mask, dev.data_ptr(), word, calls=CALLS[:1])
         # a bad value is not read when its bit is clear
         r.dispatch_adaptive_pattern(None, criteria(rm, E3, color_threshold=256), p)
-        check_frame(r, M, ref, P, "color_threshold 256 with COLOR clear")
+        check_frame(r, M, ref["A"], P, "color_threshold 256 with COLOR clear", ref["G"])
         # masks: null, and a pitch below a row
         refused(rm, r, rm.RM_ERR_INVALID, p, None, None, 0, "null mask", calls=CALLS[1:])
         refused(rm, r, rm.RM_ERR_INVALID, p, None, mask, dev.data_ptr(), "row_pitch", pitch=W - 1, calls=CALLS[1:])
-        check_frame(r, M, ref, P, "after the refusals")
+        check_frame(r, M, ref["A"], P, "after the refusals", ref["G"])

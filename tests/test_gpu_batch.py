@@ -108,7 +108,7 @@ def test_batch_sharded_and_external_output(rm, gpu):
 
 
 def _tables(rm):
-    from test_gpu_scene import floor_last_scene, random_scene
+    from scenes import floor_last_scene, random_scene
     return {"reference": rm.default_scene(), "floor": floor_last_scene(rm, 3),
             "random": random_scene(rm, 5)}
 

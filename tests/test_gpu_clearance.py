@@ -16,11 +16,11 @@ import math
 import numpy as np
 import pytest
 
-from test_gpu_fuzz_uniforms import CASES as FUZZ_CASES
-from test_gpu_fuzz_uniforms import _uniforms as fuzz_uniforms
-from test_gpu_gbuffer import gbuf_rays
-from test_gpu_parity import _compare, _production_equals_counting, _render_gpu
-from test_gpu_trace import bits_equal
+from frames import compare, production_equals_counting, render
+from records import bits_equal, gbuf_rays
+from uniforms import CASES as FUZZ_CASES
+from uniforms import H, W, aim
+from uniforms import _uniforms as fuzz_uniforms
 
 pytestmark = pytest.mark.gpu
 
@@ -57,25 +57,12 @@ COMBOS = [[(67, 41, True, 3, 0), (37, 23, False, 0, 1)],
 FRAMES = [(u, c) for j, u in enumerate(UNIFORMS) for c in COMBOS[j % 2]]
 
 
-def _aim(u, pos, look):
-    """The camera at pos looking at the point `look`: the uniform's basis (glsl:68-74
-    takes dir, xAxis and yAxis as they come), right-handed with world up (0, 1, 0)."""
-    f = np.array(look, np.float64) - np.array(pos, np.float64)
-    f /= np.linalg.norm(f)
-    x = np.cross(f, (0.0, 1.0, 0.0))
-    x /= np.linalg.norm(x)
-    y = np.cross(x, f)
-    for i in range(3):
-        u.camera.pos[i], u.camera.dir[i] = pos[i], f[i]
-        u.camera.xAxis[i], u.camera.yAxis[i] = x[i], y[i]
-
-
 def _build(rm, case, combo):
     name, frame, cam, light, itime = case
     W, H, aa, bounces, sm = combo
     u = rm.sweep_uniforms(frame, 120, bounces, aa, sm)
     if cam is not None:
-        _aim(u, cam[0], cam[1])
+        aim(u, cam[0], cam[1])
     if light is not None:
         for i in range(3):
             u.light.position[i] = light[i]
@@ -86,9 +73,9 @@ def _build(rm, case, combo):
 
 def _bar(rm, oracle, u, W, H, label):
     ref = oracle.render(u, W, H)
-    got = _render_gpu(rm, u, W, H, rm.RM_KERNEL_PIXEL)
-    _compare(ref, got, label)
-    _production_equals_counting(rm, u, W, H, rm.RM_KERNEL_PIXEL, got, label)
+    got = render(rm, u, W, H, kernel=rm.RM_KERNEL_PIXEL)
+    compare(ref, got, label)
+    production_equals_counting(rm, u, W, H, rm.RM_KERNEL_PIXEL, got, label)
     return got
 
 
@@ -153,7 +140,6 @@ def _low_case(i):
 def test_low_camera_fuzz(rm, oracle, gpu, i):
     assert len(FUZZ_CASES) >= NFUZZ
     c = _low_case(i)
-    from test_gpu_fuzz_uniforms import H, W
     u = fuzz_uniforms(rm, c)
     if i % 2:
         # the generator's cameras have no yAxis (rm.Camera before its lookAt()): every

@@ -21,8 +21,8 @@ import math
 import numpy as np
 import pytest
 
-from test_gpu_clearance import _aim
-from test_gpu_parity import _compare, _render_gpu
+from frames import compare, render
+from uniforms import aim
 
 pytestmark = pytest.mark.gpu
 
@@ -41,9 +41,9 @@ def _flags(rm, u):
 def _three(rm, oracle, u, label, w=W, h=H):
     ref = oracle.render(u, w, h)
     k = rm.RM_KERNEL_PIXEL
-    counted = _render_gpu(rm, u, w, h, k)
-    _compare(ref, counted, label)
-    prod = _render_gpu(rm, u, w, h, k, counters=False)
+    counted = render(rm, u, w, h, kernel=k)
+    compare(ref, counted, label)
+    prod = render(rm, u, w, h, kernel=k, counters=False)
     np.testing.assert_array_equal(prod["rgba32f"].view(np.uint32), counted["rgba32f"].view(np.uint32),
                                   err_msg=f"{label}: production RGBA32F against the counting build's, bitwise")
     np.testing.assert_array_equal(np.isnan(prod["rgba32f"]), np.isnan(counted["rgba32f"]),
@@ -158,7 +158,7 @@ def test_quantize(rm, oracle, gpu, case):
 def _horizon_camera(u):
     """Pitched slightly down and rolled by 12 degrees: the horizon crosses the tile rows
     at a slant, with the spheres, the blend and the torus in view."""
-    _aim(u, (6.0, 1.0, 32.0), (-1.0, -2.5, -6.0))
+    aim(u, (6.0, 1.0, 32.0), (-1.0, -2.5, -6.0))
     a = math.radians(12.0)
     x = np.array(list(u.camera.xAxis)[:3], np.float64)
     y = np.array(list(u.camera.yAxis)[:3], np.float64)
@@ -178,7 +178,7 @@ def test_downward_loop_switch(rm, oracle, gpu, bounces):
     # for each of the 4 x bounces reflected marches leaves one march with more than 16.
     u0 = rm.sweep_uniforms(60, 120, 0, True, 0)
     _horizon_camera(u0)
-    base = _render_gpu(rm, u0, W, H, rm.RM_KERNEL_PIXEL)
+    base = render(rm, u0, W, H, kernel=rm.RM_KERNEL_PIXEL)
     extra = counted["sdf_counts"].astype(np.int64) - base["sdf_counts"].astype(np.int64)
     assert extra.max() > 4 * (4 * bounces + 32) + 4 * bounces * 16, extra.max()
     # the horizon is in the frame, and not along a tile row: sky and floor in most rows

@@ -1,5 +1,5 @@
 """GPU parity of runtime scene tables under seeded random uniforms: the tables of
-test_gpu_scene.py (random entries of every type, with and without extra planes,
+tests/scenes.py (random entries of every type, with and without extra planes,
 and reference-shaped floor-last tables) seen from the random cameras and lights
 of test_gpu_fuzz_uniforms.py.
 
@@ -13,9 +13,9 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_fuzz_uniforms import CASES as UCASES, H, W, _uniforms
-from test_gpu_parity import _compare
-from test_gpu_scene import _render, _render_spec, _same, floor_last_scene, random_scene
+from frames import compare, render, same
+from scenes import floor_last_scene, random_scene
+from uniforms import CASES as UCASES, H, W, _uniforms
 
 pytestmark = pytest.mark.gpu
 
@@ -39,9 +39,9 @@ def _case(rm, i):
 def test_random_tables_random_uniforms(rm, oracle, gpu, i):
     scene, u = _case(rm, i)
     ref = oracle.render(u, W, H, scene=scene)
-    got = _render(rm, u, W, H, scene=scene)
-    _compare(ref, got, f"table case {i}")
-    prod = _render(rm, u, W, H, scene=scene, counters=False)
+    got = render(rm, u, W, H, scene=scene)
+    compare(ref, got, f"table case {i}")
+    prod = render(rm, u, W, H, scene=scene, counters=False)
     np.testing.assert_array_equal(prod["rgba32f"], got["rgba32f"], err_msg=f"table case {i}")
     np.testing.assert_array_equal(prod["rgba8"], got["rgba8"], err_msg=f"table case {i}")
 
@@ -50,5 +50,5 @@ def test_random_tables_random_uniforms(rm, oracle, gpu, i):
 def test_specialised_random_uniforms_equal_generic(rm, gpu, i):
     scene, u = _case(rm, i)
     for counters in (True, False):
-        _same(_render_spec(rm, u, W, H, scene, counters=counters),
-              _render(rm, u, W, H, scene=scene, counters=counters))
+        same(render(rm, u, W, H, scene, counters=counters, specialize=True),
+             render(rm, u, W, H, scene=scene, counters=counters))

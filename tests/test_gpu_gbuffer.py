@@ -19,8 +19,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_scene import floor_last_scene, random_scene
-from test_gpu_trace import bits_equal, oracle_normals
+from frames import ALL, renderer
+from records import gbuf_rays, oracle_gbuffer, records_equal
+from scenes import scene_of
+from uniforms import main_u, off_sweep_uniforms
 
 pytestmark = pytest.mark.gpu
 
@@ -28,44 +30,8 @@ F32 = np.float32
 W0, H0 = 130, 67
 SHAPES = [(130, 67), (37, 23), (1, 1)]
 FIELDS = ("t", "id", "normal", "albedo")
-ALL = 7  # RM_OUT_RGBA8 | RM_OUT_RGBA32F | RM_OUT_GBUFFER
 HITN = 2  # RM_TRACE_HIT | RM_TRACE_NORMAL
 MISSES = {False: 3565, True: 3603}
-
-
-def main_u(rm, aa, bounces=1, shadow=0):
-    return rm.sweep_uniforms(60, 120, bounces, aa, shadow)
-
-
-_rays = {}
-
-
-def gbuf_rays(oracle, u, W, H, aa):
-    """Every pixel's G-buffer ray, [H * W, 3] origins and directions, row 0 the bottom row."""
-    key = (bytes(u.camera), W, H, bool(aa))
-    if key not in _rays:
-        o, d = np.zeros((H, W, 3), F32), np.zeros((H, W, 3), F32)
-        for py in range(H):
-            for px in range(W):
-                uvx = F32(px * 2 - W) / F32(W)  # glsl:301-305, in float32
-                uvy = F32(py * 2 - H) / F32(H)
-                if aa:  # the first sample's offsets (glsl:311-313)
-                    uvx = F32(uvx + F32(0.25) / F32(W))
-                    uvy = F32(uvy + F32(0.25) / F32(H))
-                o[py, px], d[py, px] = oracle.cast_ray(u, float(uvx), float(uvy))
-        o, d = o.reshape(-1, 3), d.reshape(-1, 3)
-        o.setflags(write=False)
-        d.setflags(write=False)
-        _rays[key] = (o, d)
-    return _rays[key]
-
-
-def records_equal(g, want, what):
-    """G-buffer pixels against records with the same field names (rm_ray_hit, or GBUFFER_DTYPE)."""
-    g, want = g.reshape(-1), want.reshape(-1)
-    assert len(g) == len(want), what
-    for f in FIELDS:
-        bits_equal(g[f], want[f], f"{what} {f}")
 
 
 def miss_record(rm):
@@ -74,18 +40,8 @@ def miss_record(rm):
     return m[0]
 
 
-def scene_of(rm, which):
-    if which == "builtin":
-        return None
-    if which == "default_table":
-        return rm.default_scene()
-    return floor_last_scene(rm, 0) if which == "floor0" else random_scene(rm, int(which[-1]))
-
-
 def render_gbuf(rm, u, W, H, scene=None, outputs=ALL, **kw):
-    with rm.Renderer(W, H, outputs=outputs, **kw) as r:
-        if scene is not None:
-            r.set_scene(scene)
+    with renderer(rm, W, H, scene, outputs, **kw) as r:
         r.dispatch(u)
         out = {"gbuf": r.read_gbuffer()}
         if outputs & rm.RM_OUT_RGBA8:
@@ -99,14 +55,11 @@ def render_gbuf(rm, u, W, H, scene=None, outputs=ALL, **kw):
 @pytest.mark.parametrize("which", ["builtin", "random0", "random1", "floor0"])
 def test_colour_untouched(rm, gpu, which):
     scene = scene_of(rm, which)
-    with rm.Renderer(W0, H0, outputs=3) as plain, rm.Renderer(W0, H0, outputs=ALL) as g:
-        for r in (plain, g):
-            if scene is not None:
-                r.set_scene(scene)
+    with renderer(rm, W0, H0, scene) as plain, renderer(rm, W0, H0, scene, ALL) as g:
         for aa in (False, True):
             for bounces in (0, 2):
                 for shadow in (0, 1):
-                    u = main_u(rm, aa, bounces, shadow)
+                    u = main_u(rm, bounces, shadow, aa)
                     plain.dispatch(u)
                     g.dispatch(u)
                     what = f"{which} aa{int(aa)} b{bounces} s{shadow}"
@@ -121,14 +74,9 @@ def test_colour_untouched(rm, gpu, which):
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_against_the_oracle(rm, oracle, gpu, shape, aa):
     W, H = shape
-    u = main_u(rm, aa)
+    u = main_u(rm, aa=aa)
     g = render_gbuf(rm, u, W, H)["gbuf"].reshape(-1)
-    o, d = gbuf_rays(oracle, u, W, H, aa)
-    want = np.zeros(W * H, rm.GBUFFER_DTYPE)
-    for i in range(W * H):
-        h, _ = oracle.raymarch(u, o[i], d[i], False)
-        want[i]["t"], want[i]["id"], want[i]["albedo"] = h.hitpoint, h.id, tuple(h.color)
-    want["normal"] = oracle_normals(oracle, u, o, d, want["t"])
+    want = oracle_gbuffer(rm, oracle, u, W, H, aa).reshape(-1)
     miss = want["t"] == F32(-1.0)
     print(f"{W}x{H} aa={aa}: ids {sorted(set(want['id'].tolist()))}, {miss.sum()} misses")
     if shape == (W0, H0):
@@ -136,7 +84,7 @@ def test_against_the_oracle(rm, oracle, gpu, shape, aa):
         assert miss.sum() == MISSES[aa]
         # (the same condition on the G-buffer itself)
         assert sorted(set(g["id"].tolist())) == [-1, 0, 1, 4, 5, 6, 7] and (g["t"] == F32(-1.0)).any()
-    records_equal(g, want, f"{W}x{H} aa={aa} vs oracle")
+    records_equal(g, want, FIELDS, f"{W}x{H} aa={aa} vs oracle")
     assert g[miss].tobytes() == miss_record(rm).tobytes() * int(miss.sum()), "a miss: t -1, id -1, zeros"
 
 
@@ -145,29 +93,27 @@ def test_against_the_oracle(rm, oracle, gpu, shape, aa):
 @pytest.mark.parametrize("which", ["builtin", "random0", "random1", "floor0"])
 def test_against_ray_queries(rm, oracle, gpu, which, aa):
     scene = scene_of(rm, which)
-    u = main_u(rm, aa)
+    u = main_u(rm, aa=aa)
     for W, H in SHAPES:
-        with rm.Renderer(W, H, outputs=ALL) as r:
-            if scene is not None:
-                r.set_scene(scene)
+        with renderer(rm, W, H, scene, ALL) as r:
             r.dispatch(u)
             g = r.read_gbuffer()
             o, d = gbuf_rays(oracle, u, W, H, aa)
             tr = r.trace(o, d, HITN)
-            records_equal(g, tr, f"{which} {W}x{H} aa={aa} vs trace")
+            records_equal(g, tr, FIELDS, f"{which} {W}x{H} aa={aa} vs trace")
             assert not tr["color"].any()
             if not aa:  # the pixel's one ray is the ray rm_pick casts
                 for px, py in {(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (W // 2, H // 2)}:
                     p = np.asarray(r.pick(px, py)).reshape(1)
-                    records_equal(g[py:py + 1, px], p, f"{which} pick {px},{py}")
+                    records_equal(g[py:py + 1, px], p, FIELDS, f"{which} pick {px},{py}")
 
 
 @pytest.mark.parametrize("aa", [False, True], ids=["noaa", "aa"])
 def test_default_table_equals_builtin(rm, gpu, aa):
-    u = main_u(rm, aa, 2)
+    u = main_u(rm, 2, aa=aa)
     a = render_gbuf(rm, u, W0, H0)
     b = render_gbuf(rm, u, W0, H0, scene=rm.default_scene())
-    records_equal(b["gbuf"], a["gbuf"], "default table vs built-in")
+    records_equal(b["gbuf"], a["gbuf"], FIELDS, "default table vs built-in")
     assert b["rgba8"].tobytes() == a["rgba8"].tobytes()
     np.testing.assert_array_equal(b["rgba32f"].view(np.uint32), a["rgba32f"].view(np.uint32))
 
@@ -176,7 +122,7 @@ def test_default_table_equals_builtin(rm, gpu, aa):
 @pytest.mark.parametrize("which", ["default_table", "random0"])
 def test_specialize_changes_nothing(rm, gpu, which):
     scene = scene_of(rm, which)
-    u = main_u(rm, True, 2)
+    u = main_u(rm, 2, aa=True)
     with rm.Renderer(W0, H0, outputs=ALL) as r:
         r.set_scene(scene)
         r.dispatch(u)
@@ -187,24 +133,15 @@ def test_specialize_changes_nothing(rm, gpu, which):
         assert (r.read_gbuffer().tobytes(), r.read_rgba8().tobytes(), r.read_rgba32f().tobytes()) == before
         r.set_scene(scene)  # a table set with the switch on
         assert r.scene_kernel_waves() == 0
-        r.dispatch(main_u(rm, False, 2))
+        r.dispatch(main_u(rm, 2))
         r.dispatch(u)
         assert (r.read_gbuffer().tobytes(), r.read_rgba8().tobytes(), r.read_rgba32f().tobytes()) == before
 
 
 # ---- 5. uniforms off the sweep ---------------------------------------------------------------
-def _fuzz_uniforms(rm, i):
-    import test_gpu_fuzz_uniforms as fz
-    if i < 16:
-        return fz._uniforms(rm, fz.CASES[i]), (fz.W, fz.H)
-    u = fz._uniforms(rm, fz.CASES[0])  # one non-finite camera
-    u.camera.pos[0] = float("nan")
-    return u, (fz.W, fz.H)
-
-
 @pytest.mark.parametrize("i", range(17), ids=[f"case{i}" for i in range(16)] + ["nan_camera"])
 def test_off_sweep_uniforms(rm, oracle, gpu, i):
-    u, (W, H) = _fuzz_uniforms(rm, i)
+    u, (W, H) = off_sweep_uniforms(rm, i)
     assert (W, H) == (67, 41)
     aa = bool(u.AA)
     with rm.Renderer(W, H, outputs=ALL) as r, rm.Renderer(W, H, outputs=3) as plain:
@@ -213,7 +150,7 @@ def test_off_sweep_uniforms(rm, oracle, gpu, i):
         g = r.read_gbuffer()
         o, d = gbuf_rays(oracle, u, W, H, aa)
         with np.errstate(all="ignore"):
-            records_equal(g, r.trace(o, d, HITN), f"case {i} vs trace")
+            records_equal(g, r.trace(o, d, HITN), FIELDS, f"case {i} vs trace")
         assert r.read_rgba8().tobytes() == plain.read_rgba8().tobytes()
         assert r.read_rgba32f().tobytes() == plain.read_rgba32f().tobytes()
 
@@ -224,7 +161,7 @@ def test_off_sweep_uniforms(rm, oracle, gpu, i):
 def test_shards_assemble(rm, gpu, which, aa):
     W, H, R, N = W0, 67, 8, 3
     scene = scene_of(rm, which)
-    u = main_u(rm, aa)
+    u = main_u(rm, aa=aa)
     full = render_gbuf(rm, u, W, H, scene=scene)["gbuf"]
     cap = C.c_int32(0)
     rm.lib().rm_shard_rows(H, R, 0, N, 0, None, C.byref(cap))
@@ -250,7 +187,7 @@ def test_shards_assemble(rm, gpu, which, aa):
 def test_interop(rm, gpu):
     import torch
     W, H = 37, 23
-    u = main_u(rm, False)
+    u = main_u(rm)
     ref = render_gbuf(rm, u, W, H)["gbuf"]
     lib = rm.lib()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -310,7 +247,7 @@ def test_refusals(rm, gpu):
         with pytest.raises(rm.RMError) as e:
             rm.Renderer(32, 16, outputs=G | rm.RM_OUT_RGBA8, **kw)
         assert e.value.code == rm.RM_ERR_INVALID and "RM_OUT_GBUFFER" in str(e.value), kw
-    u = main_u(rm, False)
+    u = main_u(rm)
     px = np.zeros((16, 32), rm.GBUFFER_DTYPE)
     with rm.Renderer(32, 16, outputs=G | rm.RM_OUT_RGBA8) as r:
         h = r.handle
@@ -346,11 +283,9 @@ def test_refusals(rm, gpu):
 @pytest.mark.parametrize("which", ["builtin", "random0"])
 def test_gbuffer_alone(rm, gpu, which, aa):
     scene = scene_of(rm, which)
-    u = main_u(rm, aa, 2)
+    u = main_u(rm, 2, aa=aa)
     want = render_gbuf(rm, u, W0, H0, scene=scene)["gbuf"]
-    with rm.Renderer(W0, H0, outputs=rm.RM_OUT_GBUFFER) as r:
-        if scene is not None:
-            r.set_scene(scene)
+    with renderer(rm, W0, H0, scene, rm.RM_OUT_GBUFFER) as r:
         r.dispatch(u)
         assert r.read_gbuffer().tobytes() == want.tobytes()
         with pytest.raises(rm.RMError) as e:

@@ -12,10 +12,9 @@ Bar:
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from frames import compare, production_equals_counting, render
 
-RGBA8_TOL = 1          # LSB, asserted (north_star: +-2)
-RGBA32F_TOL = 2.0e-6   # absolute, colours are O(1): ~16 ULP at 1.0
+pytestmark = pytest.mark.gpu
 
 # (frame, bounces, AA, shadow_mode) — frame -1 is the default start-up frame D.
 CASES = [
@@ -36,32 +35,6 @@ CASES = [
 ]
 
 
-def _render_gpu(rm, u, W, H, kernel, counters=True, outputs=None):
-    outputs = outputs or (rm.RM_OUT_RGBA8 | rm.RM_OUT_RGBA32F)
-    with rm.Renderer(W, H, outputs=outputs, kernel=kernel, counters=counters) as r:
-        r.dispatch(u)
-        out = {"rgba8": r.read_rgba8(), "rgba32f": r.read_rgba32f()}
-        if counters:
-            out["counters"] = r.counters()
-            out["sdf_counts"] = r.sdf_counts()
-    return out
-
-
-def _compare(ref, got, label):
-    np.testing.assert_array_equal(got["sdf_counts"], ref["sdf_counts"],
-                                  err_msg=f"{label}: per-pixel sdf counts differ (geometry)")
-    assert got["counters"] == ref["counters"], f"{label}: counters differ"
-    d8 = np.abs(got["rgba8"].astype(np.int16) - ref["rgba8"].astype(np.int16))
-    assert d8.max() <= RGBA8_TOL, f"{label}: RGBA8 max|d|={d8.max()} ({(d8 > 0).sum()} px)"
-    # the reference itself yields NaN for some uniforms (camera inside a
-    # primitive); NaN must appear exactly where the oracle has it
-    fin = np.isfinite(ref["rgba32f"])
-    np.testing.assert_array_equal(np.isfinite(got["rgba32f"]), fin, err_msg=f"{label}: NaN/inf mask")
-    df = np.abs(got["rgba32f"] - ref["rgba32f"])[fin]
-    assert df.size == 0 or df.max() <= RGBA32F_TOL, f"{label}: RGBA32F max|d|={df.max()}"
-    return int(d8.max()), float(df.max()) if df.size else 0.0
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"f{c[0]}_b{c[1]}_aa{int(c[2])}_s{c[3]}")
 @pytest.mark.parametrize("shape", [(96, 64), (100, 70)], ids=["96x64", "100x70"])
 def test_parity_vs_oracle(rm, oracle, gpu, case, shape):
@@ -70,17 +43,9 @@ def test_parity_vs_oracle(rm, oracle, gpu, case, shape):
     u = rm.sweep_uniforms(f, 120, b, aa, sm)
     ref = oracle.render(u, W, H)
     k = rm.RM_KERNEL_PIXEL
-    got = _render_gpu(rm, u, W, H, k)
-    _compare(ref, got, f"{shape} {case}")
-    _production_equals_counting(rm, u, W, H, k, got, f"{shape} {case}")
-
-
-def _production_equals_counting(rm, u, W, H, k, counted, label):
-    """The production build (no counters) takes the proof-based early exits
-    that the counting build only checks; both must give the same image."""
-    prod = _render_gpu(rm, u, W, H, k, counters=False)
-    np.testing.assert_array_equal(prod["rgba32f"], counted["rgba32f"], err_msg=label)
-    np.testing.assert_array_equal(prod["rgba8"], counted["rgba8"], err_msg=label)
+    got = render(rm, u, W, H, kernel=k)
+    compare(ref, got, f"{shape} {case}")
+    production_equals_counting(rm, u, W, H, k, got, f"{shape} {case}")
 
 
 @pytest.mark.parametrize("shape", [(1, 1), (3, 1), (1, 5), (37, 23), (65, 3), (130, 67)])
@@ -88,23 +53,23 @@ def test_ragged_shapes(rm, oracle, gpu, shape):
     W, H = shape
     u = rm.sweep_uniforms(45, 120, 2, True, 0)
     ref = oracle.render(u, W, H)
-    got = _render_gpu(rm, u, W, H, rm.RM_KERNEL_PIXEL)
-    _compare(ref, got, f"shape {shape}")
-    _production_equals_counting(rm, u, W, H, rm.RM_KERNEL_PIXEL, got, f"shape {shape}")
+    got = render(rm, u, W, H, kernel=rm.RM_KERNEL_PIXEL)
+    compare(ref, got, f"shape {shape}")
+    production_equals_counting(rm, u, W, H, rm.RM_KERNEL_PIXEL, got, f"shape {shape}")
 
 
 def test_rgba8_is_quantized_rgba32f(rm, gpu):
     W, H = 128, 72
     u = rm.sweep_uniforms(10, 120, 3, True, 0)
-    g = _render_gpu(rm, u, W, H, rm.RM_KERNEL_AUTO, counters=False)
+    g = render(rm, u, W, H, kernel=rm.RM_KERNEL_AUTO, counters=False)
     np.testing.assert_array_equal(g["rgba8"], rm.quantize_rgba8(g["rgba32f"]))
 
 
 def test_counter_mode_does_not_change_image(rm, gpu):
     W, H = 160, 90
     u = rm.sweep_uniforms(33, 120, 3, True, 0)
-    a = _render_gpu(rm, u, W, H, rm.RM_KERNEL_PIXEL, counters=True)
-    b = _render_gpu(rm, u, W, H, rm.RM_KERNEL_PIXEL, counters=False)
+    a = render(rm, u, W, H, kernel=rm.RM_KERNEL_PIXEL, counters=True)
+    b = render(rm, u, W, H, kernel=rm.RM_KERNEL_PIXEL, counters=False)
     np.testing.assert_array_equal(a["rgba32f"], b["rgba32f"])
 
 
@@ -154,6 +119,6 @@ def test_stress_uniforms(rm, oracle, gpu, case, bounces, aa, sm):
             u.camera.pos[i] = cam[i]
     ref = oracle.render(u, W, H)
     k = rm.RM_KERNEL_PIXEL
-    got = _render_gpu(rm, u, W, H, k)
-    _compare(ref, got, name)
-    _production_equals_counting(rm, u, W, H, k, got, name)
+    got = render(rm, u, W, H, kernel=k)
+    compare(ref, got, name)
+    production_equals_counting(rm, u, W, H, k, got, name)

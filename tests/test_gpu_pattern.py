@@ -5,107 +5,23 @@ Every frame is rm_sweep_uniforms(60, 120, b, ., s) on a context with both colour
 The shapes: 37 x 23 is ragged for the 4x4 tiles on both axes, 9 x 5 and 1 x 1 are the
 small cases, and 261 x 6 has 66 tile columns, past one 64-block window of tile_col.
 
-"Model" is the header's rule with nothing of the frame kernels in it: the uv from
-rm_pattern_uv_table (held against numpy by tests/test_pattern_abi.py), the rays from the
-oracle's castRay, the colours from the same context's SHADE trace of those rays, the sum
-and the quantisation in numpy float32 (tests/sample_pattern_model.py).  RGBA32F is
-compared as uint32 wherever the expected value is not NaN and NaN-for-NaN elsewhere,
-RGBA8 byte for byte.
+"Model" is the header's rule with nothing of the frame kernels in it (tests/patterns.py
+model, equals_model); the plain AA-off and AA-on frames are tests/frames.py refs' A and B.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import sample_pattern_model as M
-from test_gpu_scene import floor_last_scene, random_scene
+from frames import images, refs, renderer, same_frame
+from patterns import equals_model, model, patterns
+from scenes import scene_of
+from uniforms import main_u
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(37, 23), (9, 5), (1, 1), (261, 6)]
-BOTH = 3  # RM_OUT_RGBA8 | RM_OUT_RGBA32F
 SCENES = ["builtin", "default-table", "random-table"]
-
-
-def scene_of(rm, name):
-    return {"builtin": None, "default-table": rm.default_scene(), "random-table": random_scene(rm, 0),
-            "floor-table": floor_last_scene(rm, 0)}[name]
-
-
-def main_u(rm, bounces=1, shadow=0, aa=False):
-    return rm.sweep_uniforms(60, 120, bounces, aa, shadow)
-
-
-def images(r):
-    return r.read_rgba8(), r.read_rgba32f()
-
-
-def renderer(rm, W, H, scene=None, **kw):
-    r = rm.Renderer(W, H, **{"outputs": BOTH, **kw})
-    if scene is not None:
-        r.set_scene(scene)
-    return r
-
-
-_plain = {}
-
-
-def plain(rm, name, W, H, bounces, shadow, aa):
-    """rm_dispatch's frame (rgba8, rgba32f) of the scene `name`, computed once."""
-    key = (name, W, H, bounces, shadow, aa)
-    if key not in _plain:
-        with renderer(rm, W, H, scene_of(rm, name)) as r:
-            r.dispatch(main_u(rm, bounces, shadow, aa))
-            _plain[key] = images(r)
-        for x in _plain[key]:
-            x.setflags(write=False)
-    return _plain[key]
-
-
-def same_frame(got, want, what):
-    assert got[0].tobytes() == want[0].tobytes(), f"{what}: rgba8, {int((got[0] != want[0]).any(-1).sum())} pixels differ"
-    np.testing.assert_array_equal(got[1].view(np.uint32), want[1].view(np.uint32), err_msg=f"{what}: rgba32f")
-
-
-def model(rm, oracle, r, u, p):
-    """(rgba8, rgba32f) of pattern p's frame of u by the rule, the colours from r's SHADE trace."""
-    W, H, n = r.width, r.height, int(p.n)
-    uvx, uvy = rm.pattern_uv_table(p, W, H)
-    o, d = np.empty((H, W, n, 3), np.float32), np.empty((H, W, n, 3), np.float32)
-    for py in range(H):
-        for px in range(W):
-            for s in range(n):
-                o[py, px, s], d[py, px, s] = oracle.cast_ray(u, float(uvx[px, s]), float(uvy[py, s]))
-    r.set_uniforms(u)
-    col = r.trace(o.reshape(-1, 3), d.reshape(-1, 3), rm.RM_TRACE_SHADE)["color"].reshape(H, W, n, 3)
-    f32 = M.pixel_sum(np.moveaxis(col, 2, 0))
-    return M.quantize(f32), f32
-
-
-def equals_model(got, want, what):
-    g8, g32 = got
-    w8, w32 = want
-    assert g32.shape == w32.shape and g8.shape == w8.shape
-    nan = np.isnan(w32)
-    assert np.isnan(g32[nan]).all(), f"{what}: NaN for NaN"
-    bad = (g32.view(np.uint32) != w32.view(np.uint32)) & ~nan
-    assert not bad.any(), f"{what}: rgba32f differs in {int(bad.any(-1).sum())} pixels, first at {np.argwhere(bad)[0]}"
-    assert g8.tobytes() == w8.tobytes(), f"{what}: rgba8, {int((g8 != w8).any(-1).sum())} pixels differ"
-
-
-def random_patterns(rm):
-    rng = np.random.default_rng(21)
-    a = rng.uniform(-1.5, 1.5, (2, 7)).astype(np.float32)
-    c = rng.uniform(-0.2, 0.2, (2, 16)).astype(np.float32)
-    return {"abs7": rm.custom_pattern(a[0], a[1]), "cum16": rm.custom_pattern(c[0], c[1], cumulative=True),
-            "jitter1": rm.custom_pattern([0.3125], [-0.21875])}
-
-
-def patterns(rm):
-    out = {"grid2": rm.sample_pattern(rm.RM_PATTERN_GRID2), "rgss": rm.sample_pattern(rm.RM_PATTERN_RGSS),
-           "grid3": rm.sample_pattern(rm.RM_PATTERN_GRID3), "grid4": rm.sample_pattern(rm.RM_PATTERN_GRID4)}
-    out.update(random_patterns(rm))
-    return out
 
 
 # ---- 1, 2. the two anchors: the AA-on and the AA-off frame ----------------------------------------
@@ -117,7 +33,7 @@ def test_reference_pattern_is_the_aa_frame(rm, gpu, W, H, name):
         for bounces in (0, 2):
             for shadow in (0, 1):
                 r.dispatch_pattern(main_u(rm, bounces, shadow), ref)
-                same_frame(images(r), plain(rm, name, W, H, bounces, shadow, True), f"{name} {W}x{H} b{bounces} s{shadow}")
+                same_frame(images(r), refs(rm, W, H, bounces, shadow, name)["B"], f"{name} {W}x{H} b{bounces} s{shadow}")
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -128,9 +44,9 @@ def test_one_centre_sample_is_the_plain_frame(rm, gpu, W, H, name):
         for bounces in (0, 2):
             for shadow in (0, 1):
                 r.dispatch_pattern(main_u(rm, bounces, shadow), centre)
-                same_frame(images(r), plain(rm, name, W, H, bounces, shadow, False), f"{name} {W}x{H} b{bounces} s{shadow}")
+                same_frame(images(r), refs(rm, W, H, bounces, shadow, name)["A"], f"{name} {W}x{H} b{bounces} s{shadow}")
     if (W, H) == (37, 23):  # the anchors are two different frames
-        assert plain(rm, name, W, H, 2, 0, False)[0].tobytes() != plain(rm, name, W, H, 2, 0, True)[0].tobytes()
+        assert refs(rm, W, H, 2, 0, name)["A"][0].tobytes() != refs(rm, W, H, 2, 0, name)["B"][0].tobytes()
 
 
 # ---- 3. every other pattern against the model ---------------------------------------------------
@@ -178,7 +94,7 @@ def test_sixteen_pixel_offsets(rm, oracle, gpu, name):
         r.dispatch_pattern(u, p)
         got = images(r)
         equals_model(got, model(rm, oracle, r, u, p), f"{name} +-16")
-    assert got[0].tobytes() != plain(rm, name, W, H, 2, 0, False)[0].tobytes()
+    assert got[0].tobytes() != refs(rm, W, H, 2, 0, name)["A"][0].tobytes()
 
 
 # ---- 6. one colour output ----------------------------------------------------------------------------
@@ -247,9 +163,7 @@ def test_specialised_context_gives_the_same_image(rm, gpu):
     with renderer(rm, W, H, scene) as r:
         r.dispatch_pattern(u, p)
         want = images(r)
-    with rm.Renderer(W, H, outputs=BOTH) as r:
-        r.specialize_scene(True)
-        r.set_scene(scene)
+    with renderer(rm, W, H, scene, specialize=True) as r:
         r.dispatch_pattern(u, p)
         same_frame(images(r), want, "specialised")
         r.dispatch_pattern(u, rm.sample_pattern(rm.RM_PATTERN_REFERENCE))

@@ -12,20 +12,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from uniforms import default_u
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-BOX = ([-30, -5, -35], [20, 15, 20])  # the scene's box (test_gpu_trace.py random_rays)
+BOX = ([-30, -5, -35], [20, 15, 20])  # the scene's box (tests/records.py random_rays)
 SPHERE = (15.0, 0.0, -10.0)
-IDS = {0, 1, 4, 5, 6, 7}              # every object and the floor (test_gpu_trace.py AIMED_IDS)
+IDS = {0, 1, 4, 5, 6, 7}              # every object and the floor (tests/test_gpu_trace.py AIMED_IDS)
 MESH_GRID = ((10.4, -4.6, -14.1), (0.9, 0.9, 0.9), (12, 10, 9))  # around the sphere
 ID_GRID = ((10.0, -4.0, -14.0), (1.2, 1.2, 1.2), (9, 7, 5))      # through it
-
-
-def default_u(rm):
-    u = rm.default_uniforms()
-    u.iTime = 1.0
-    return u
 
 
 def make_ctx(rm, table):

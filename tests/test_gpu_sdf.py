@@ -13,25 +13,16 @@ import numpy as np
 import pytest
 
 import sdf_model as M
-from test_gpu_scene import floor_last_scene, random_scene
-from test_gpu_trace import bits_equal, pixel_rays, zeros
+from grids import desc, grid_points
+from records import bits_equal, pixel_rays, records_equal, zeros
+from scenes import random_scene, scene_of
+from uniforms import default_u
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 NAN, INF = float("nan"), float("inf")
 FIELDS = ("t", "id", "material", "albedo", "normal", "color")
-
-
-def default_u(rm, itime=1.0):
-    u = rm.default_uniforms()
-    u.iTime = itime
-    return u
-
-
-def records_equal(got, want, what):
-    for f in FIELDS:
-        bits_equal(got[f], want[f], f"{what} {f}")
 
 
 def all_points():
@@ -44,22 +35,10 @@ def ctx(rm, gpu):
         yield r
 
 
-def desc(rm, origin, step, dims):
-    return rm.rm_sdf_grid_desc((C.c_float * 3)(*origin), (C.c_float * 3)(*step), (C.c_int32 * 3)(*dims))
-
-
-def grid_points(origin, step, dims):
-    """The grid's coordinates in float32: one multiply, then one add per axis; x fastest."""
-    with np.errstate(all="ignore"):
-        ax = [F32(origin[a]) + np.arange(dims[a], dtype=F32) * F32(step[a]) for a in range(3)]
-    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
-    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1).astype(F32)
-
-
 # ---- 1. the seeded set against the oracle ----------------------------------------------
 @pytest.mark.parametrize("itime", [1.0, 0.0, 4.5])
 def test_seeded_points_bit_exact(rm, oracle, ctx, itime):
-    u = default_u(rm, itime)
+    u = default_u(rm, itime=itime)
     pts = M.seeded_points()
     want = M.oracle_records(rm, oracle, u, pts, normal=True)
     if itime == 1.0:  # the set's coverage, a condition on the oracle's answers alone
@@ -67,23 +46,23 @@ def test_seeded_points_bit_exact(rm, oracle, ctx, itime):
         assert int((want["t"] < 0).sum()) == 186
     ctx.set_uniforms(u)
     got = ctx.sdf(pts, rm.RM_SDF_NORMAL)
-    records_equal(got, want, f"NORMAL iTime {itime}")
+    records_equal(got, want, FIELDS, f"NORMAL iTime {itime}")
     got = ctx.sdf(pts)
-    records_equal(got, M.oracle_records(rm, oracle, u, pts), f"VALUE iTime {itime}")
+    records_equal(got, M.oracle_records(rm, oracle, u, pts), FIELDS, f"VALUE iTime {itime}")
     assert zeros(got["normal"]) and zeros(got["color"])
 
 
 # ---- 2. edge points: fast and literal lanes in one wave --------------------------------
 @pytest.mark.parametrize("itime", [1.0, 4.5])
 def test_edge_points_bit_exact(rm, oracle, ctx, itime):
-    u = default_u(rm, itime)
+    u = default_u(rm, itime=itime)
     pts = M.edge_points()
     want = M.oracle_records(rm, oracle, u, pts, normal=True)
     assert np.isnan(want["normal"][[14, 15]]).all(), "zero gradient far from the origin: a NaN normal"
     assert np.isnan(want["t"][[3, 5]]).all() and (want["id"][[3, 5]] == 7).all(), "a NaN distance: the last entry"
     ctx.set_uniforms(u)
-    records_equal(ctx.sdf(pts, rm.RM_SDF_NORMAL), want, "edge NORMAL")
-    records_equal(ctx.sdf(pts), M.oracle_records(rm, oracle, u, pts), "edge VALUE")
+    records_equal(ctx.sdf(pts, rm.RM_SDF_NORMAL), want, FIELDS, "edge NORMAL")
+    records_equal(ctx.sdf(pts), M.oracle_records(rm, oracle, u, pts), FIELDS, "edge VALUE")
 
 
 # ---- 3. counts -------------------------------------------------------------------------
@@ -123,20 +102,15 @@ def test_default_table_equals_builtin(rm, ctx, gpu):
         for flags in (rm.RM_SDF_VALUE, rm.RM_SDF_NORMAL):
             want = ctx.sdf(pts, flags)
             got = t.sdf(pts, flags)
-            records_equal(got, want, f"default table, flags {flags}")
+            records_equal(got, want, FIELDS, f"default table, flags {flags}")
             t.specialize_scene(True)  # queries still run the generic table code
             assert t.sdf(pts, flags).tobytes() == got.tobytes()
             t.specialize_scene(False)
 
 
-def big_scene(rm):
-    return (random_scene(rm, 4) + random_scene(rm, 5) + random_scene(rm, 6) + random_scene(rm, 7))[:30]
-
-
 @pytest.mark.parametrize("which", ["random0", "random1", "random2", "random3", "floor0", "big30"])
 def test_tables_against_the_model(rm, gpu, which):
-    scene = (floor_last_scene(rm, 0) if which == "floor0" else big_scene(rm) if which == "big30"
-             else random_scene(rm, int(which[-1])))
+    scene = scene_of(rm, which)
     assert which != "big30" or len(scene) == 30
     pts = all_points()
     with rm.Renderer(37, 23) as t:
@@ -144,9 +118,9 @@ def test_tables_against_the_model(rm, gpu, which):
         t.set_uniforms(default_u(rm))
         want = M.sdf_records(rm, scene, 1.0, pts, normal=True)
         got = t.sdf(pts, rm.RM_SDF_NORMAL)
-        records_equal(got, want, f"{which} NORMAL")
+        records_equal(got, want, FIELDS, f"{which} NORMAL")
         val = t.sdf(pts)
-        records_equal(val, M.sdf_records(rm, scene, 1.0, pts), f"{which} VALUE")
+        records_equal(val, M.sdf_records(rm, scene, 1.0, pts), FIELDS, f"{which} VALUE")
         # rm_scene_specialize on: which code a query runs depends on the context having a
         # table, not on the table, so the switch is thrown where the compile it starts is
         # short (the random tables' takes 15-20 s each; the default table's is in the test above)
@@ -169,7 +143,7 @@ def test_tie_goes_to_the_later_entry(rm, gpu, order):
         t.set_scene(scene)
         t.set_uniforms(default_u(rm))
         got = t.sdf(pts)
-        records_equal(got, want, f"tie {order}")
+        records_equal(got, want, FIELDS, f"tie {order}")
         dist, ids = t.sdf_grid((-6, -5, -10), (0.5, 0.5, 0.5), (28, 22, 28), ids=True)
         gp = grid_points((-6, -5, -10), (0.5, 0.5, 0.5), (28, 22, 28))
         gw = M.sdf_records(rm, scene, 1.0, gp)
@@ -401,7 +375,7 @@ def test_counting_context_timing_and_shards(rm, oracle, gpu):
     with rm.Renderer(37, 23, outputs=rm.RM_OUT_RGBA32F, counters=True) as r:
         r.dispatch(u)
         cnt = r.counters()
-        records_equal(r.sdf(pts, rm.RM_SDF_NORMAL), want, "counting context")
+        records_equal(r.sdf(pts, rm.RM_SDF_NORMAL), want, FIELDS, "counting context")
         r.sdf_grid((0, 0, 0), (1, 1, 1), (5, 3, 2))
         assert r.counters() == cnt
         r.synchronize()
@@ -414,7 +388,7 @@ def test_counting_context_timing_and_shards(rm, oracle, gpu):
         assert launches == 2 and ms > 0.0
     with rm.Renderer(37, 23, row_block=4, shard=1, nshards=3) as r:  # evaluates locally
         r.set_uniforms(u)
-        records_equal(r.sdf(pts, rm.RM_SDF_NORMAL), want, "sharded context")
+        records_equal(r.sdf(pts, rm.RM_SDF_NORMAL), want, FIELDS, "sharded context")
 
 
 def test_refusals(rm, oracle, ctx):
@@ -457,4 +431,4 @@ def test_refusals(rm, oracle, ctx):
         assert lib.rm_sdf_grid_device(m.handle, C.byref(g), pd, pi) == rm.RM_ERR_STATE
         assert lib.rm_last_error(m.handle)
     # the context still answers correctly afterwards
-    records_equal(ctx.sdf(pts, rm.RM_SDF_NORMAL), M.oracle_records(rm, oracle, u, pts, normal=True), "after the refusals")
+    records_equal(ctx.sdf(pts, rm.RM_SDF_NORMAL), M.oracle_records(rm, oracle, u, pts, normal=True), FIELDS, "after the refusals")

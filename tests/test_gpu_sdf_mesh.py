@@ -13,9 +13,10 @@ import pytest
 
 import sdf_mesh_model as MM
 import sdf_model as M
-from test_gpu_scene import floor_last_scene, random_scene
-from test_gpu_trace import bits_equal
-from test_sdf_mesh_model import GRIDS, grid_points
+from grids import GRIDS, desc, grid_points, step3
+from records import bits_equal
+from scenes import floor_last_scene, random_scene
+from uniforms import default_u
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +25,6 @@ NAN = float("nan")
 FIELDS = ("t", "id", "material", "albedo", "normal", "color")
 FLOOR = ((-10.3, -6.2, -3.1), (0.25, 0.5, 0.25), (130, 3, 5))  # 129 cells a row: three waves, a ragged third
 GUARD = 0xABABABAB
-
-
-def default_u(rm, itime=1.0):
-    u = rm.default_uniforms()
-    u.iTime = itime
-    return u
-
-
-def desc(rm, origin, step, dims):
-    return rm.rm_sdf_grid_desc((C.c_float * 3)(*origin), (C.c_float * 3)(*step), (C.c_int32 * 3)(*dims))
-
-
-def step3(step):
-    return (step,) * 3
 
 
 def mesh_equal(got, want, what):
@@ -85,7 +72,7 @@ def test_objects_bit_exact(rm, ctx, table_ctx, g):
     _, origin, step, dims, itime, nv, nq, _ = g
     got = {}
     for name, r in (("builtin", ctx), ("table", table_ctx)):
-        r.set_uniforms(default_u(rm, itime))
+        r.set_uniforms(default_u(rm, itime=itime))
         pos, quads, attr = r.sdf_mesh(origin, step3(step), dims, attrs=False)
         assert attr is None and pos.dtype == F32 and quads.dtype == np.uint32
         assert (len(pos), len(quads)) == (nv, nq), name
@@ -119,7 +106,7 @@ def test_blend_differs_between_two_times(rm, ctx):
     _, origin, step, dims, _, _, _, _ = GRIDS[1]
     meshes = []
     for itime in (1.0, 2.5):
-        ctx.set_uniforms(default_u(rm, itime))
+        ctx.set_uniforms(default_u(rm, itime=itime))
         pos, quads, _ = ctx.sdf_mesh(origin, step3(step), dims, attrs=False)
         mesh_equal((pos, quads), model_on_own_volume(ctx, origin, step3(step), dims), f"blend at iTime {itime}")
         meshes.append(pos)
@@ -140,7 +127,7 @@ def test_past_one_scan_round(rm, ctx):
     """(129, 129, 65) points: 3 x 129 x 65 = 25,155 waves against the scan's 16,384 a round,
     nearly all of them empty; sphere id 0 sits in the middle."""
     origin, step, dims = (8.6, -5.0, -13.2), (0.1, 0.1, 0.1), (129, 129, 65)
-    ctx.set_uniforms(default_u(rm, 0.0))
+    ctx.set_uniforms(default_u(rm, itime=0.0))
     pos, quads, _ = ctx.sdf_mesh(origin, step, dims, attrs=False)
     want = model_on_own_volume(ctx, origin, step, dims)
     assert len(want[0]) > 5000 and len(want[1]) > 5000
@@ -169,7 +156,7 @@ def test_past_one_round_of_chunk_sums(rm, gpu):
 # ---- 2. triangles, attributes ----------------------------------------------------------
 def test_triangles_are_the_split_of_quads(rm, ctx):
     _, origin, step, dims, itime, _, nq, _ = GRIDS[2]
-    ctx.set_uniforms(default_u(rm, itime))
+    ctx.set_uniforms(default_u(rm, itime=itime))
     pos, quads, _ = ctx.sdf_mesh(origin, step3(step), dims, attrs=False)
     tpos, tris, _ = ctx.sdf_mesh(origin, step3(step), dims, attrs=False, triangles=True)
     assert tris.shape == (nq, 6) and nq >= 2  # (odd and even quads store in different orders)
@@ -182,7 +169,7 @@ def test_attributes_equal_the_point_query(rm, ctx, table_ctx, table):
     r = table_ctx if table else ctx
     for g in (GRIDS[1], GRIDS[3]):
         _, origin, step, dims, itime, nv, _, _ = g
-        r.set_uniforms(default_u(rm, itime))
+        r.set_uniforms(default_u(rm, itime=itime))
         for normals in (False, True):
             pos, _, attr = r.sdf_mesh(origin, step3(step), dims, normals=normals)
             assert attr.dtype == rm.RAY_HIT_DTYPE and len(attr) == nv == len(pos)
@@ -197,7 +184,7 @@ def test_attributes_equal_the_point_query(rm, ctx, table_ctx, table):
 # ---- 3. capacities ---------------------------------------------------------------------
 def test_capacities(rm, ctx):
     _, origin, step, dims, itime, nv, nq, _ = GRIDS[0]
-    ctx.set_uniforms(default_u(rm, itime))
+    ctx.set_uniforms(default_u(rm, itime=itime))
     g = desc(rm, origin, step3(step), dims)
     pos, quads, attr = ctx.sdf_mesh(origin, step3(step), dims, normals=True)
     wp, wq, wa = pos.view(np.uint32).reshape(-1), quads.reshape(-1), attr.view(np.uint32).reshape(-1)
@@ -228,7 +215,7 @@ def test_capacities(rm, ctx):
 def test_device_call_on_a_torch_stream(rm, gpu):
     import torch
     _, origin, step, dims, itime, nv, nq, _ = GRIDS[1]
-    u = default_u(rm, itime)
+    u = default_u(rm, itime=itime)
     dev = torch.device("cuda", torch.cuda.current_device())
     with rm.Renderer(37, 23, outputs=rm.RM_OUT_RGBA8 | rm.RM_OUT_RGBA32F | rm.RM_OUT_GBUFFER) as r:
         r.set_uniforms(u)
@@ -297,7 +284,7 @@ def test_device_wrapper_on_the_contexts_own_stream(rm, gpu):
     with rm.Renderer(37, 23) as r:
         for g in (GRIDS[1], GRIDS[3]):
             _, origin, step, dims, itime, nv, nq, _ = g
-            r.set_uniforms(default_u(rm, itime))
+            r.set_uniforms(default_u(rm, itime=itime))
             pos, quads, attr = r.sdf_mesh(origin, step3(step), dims, normals=True)
             for _ in range(8):
                 busy.mul_(1.0)  # 256 MB each way per kernel, queued on torch's stream
@@ -349,7 +336,7 @@ def test_timing_counts_one_launch(rm, gpu):
     _, origin, step, dims, itime, nv, nq, _ = GRIDS[0]
     g = desc(rm, origin, step3(step), dims)
     with rm.Renderer(37, 23) as r:
-        r.set_uniforms(default_u(rm, itime))
+        r.set_uniforms(default_u(rm, itime=itime))
         r.synchronize()
         r.kernel_time_ms(reset=True)
         r.enable_timing(True)
@@ -367,7 +354,7 @@ def test_timing_counts_one_launch(rm, gpu):
 
 def test_shards_and_counters_give_the_plain_mesh(rm, ctx):
     _, origin, step, dims, itime, nv, nq, _ = GRIDS[1]
-    u = default_u(rm, itime)
+    u = default_u(rm, itime=itime)
     ctx.set_uniforms(u)
     want = ctx.sdf_mesh(origin, step3(step), dims, normals=True)
     with rm.Renderer(37, 23, row_block=4, shard=1, nshards=3) as r:  # runs locally
@@ -386,7 +373,7 @@ def test_shards_and_counters_give_the_plain_mesh(rm, ctx):
 def test_refusals(rm, ctx):
     lib = rm.lib()
     _, origin, step, dims, itime, nv, nq, _ = GRIDS[0]
-    ctx.set_uniforms(default_u(rm, itime))
+    ctx.set_uniforms(default_u(rm, itime=itime))
     g = C.byref(desc(rm, origin, step3(step), dims))
     pos = np.zeros((nv + 1) * 3, F32)
     attr = np.zeros(nv + 1, rm.RAY_HIT_DTYPE)

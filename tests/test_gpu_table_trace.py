@@ -21,8 +21,8 @@ import numpy as np
 import pytest
 
 import table_trace_rays as T
-from test_gpu_fuzz_uniforms import CASES, _uniforms
-from test_gpu_trace import bits_equal, colors_close, zeros
+from records import bits_equal, colors_close, hit_fields_equal, zeros
+from uniforms import CASES, _uniforms, default_u
 
 pytestmark = pytest.mark.gpu
 
@@ -36,8 +36,7 @@ def uniforms(rm, which, bounces=0, mode=0):
     """"default": the defaults at iTime 1; "moved": a fuzz case's camera and light at
     iTime 4.5, so the blend entries move too."""
     if which == "default":
-        u = rm.default_uniforms()
-        u.iTime = 1.0
+        u = default_u(rm)
     else:
         u = _uniforms(rm, MOVED)
         u.iTime = 4.5
@@ -182,8 +181,7 @@ def test_shade(rm, oracle, ctx, name, mode, bounces):
         what = f"{name} {which} shade b{bounces} s{mode}"
         got = both_orders(ctx, name, o, d, rm.RM_TRACE_SHADE, what)
         want = oracle_hits(oracle, u, o, d, rm.RM_TRACE_SHADE, scene, name)
-        for f in ("t", "id", "material", "albedo"):
-            bits_equal(got[f], want[f], f"{what} {f}")
+        hit_fields_equal(got, want, what)
         assert zeros(got["normal"]), what
         colors_close(got["color"], want["color"], what)
 

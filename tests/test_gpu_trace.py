@@ -6,143 +6,22 @@ Geometry (t, id, material, albedo, normals, shadow factors) is compared bit for
 bit as uint32, a NaN equal to a NaN; colours within 2e-6 (DESIGN §5's RGBA32F bar:
 pow is the only operation that differs), NaN masks equal.
 
-Ray sets (uniforms: the defaults with iTime = 1 unless a test says otherwise):
-  aimed   7 unit rays from (0, 10, 15) at each object, the floor and the sky;
-  random  1000 seeded rays through the scene's box (every object, the floor, misses);
-  edge    rays outside the fast lanes' predicate or at its borders: rd = 0, NaN,
-          1e30, 1e-3, 1e3 long; ro = 1e20, inf; on the floor; grazing it.
+The ray sets (aimed, random, edge), the comparisons and the oracle per ray are
+tests/records.py's; uniforms: the defaults with iTime = 1 unless a test says otherwise.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from test_gpu_scene import floor_last_scene, random_scene
+from records import (F32, FLAG_SETS, INF, SETS, aimed_rays, bits_equal, colors_close, edge_rays, hit_fields_equal,
+                     oracle_colors, oracle_march, oracle_normals, pixel_rays, random_rays, zeros)
+from scenes import scene_of
+from uniforms import default_u
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-NAN, INF = float("nan"), float("inf")
-TOL = 2e-6
-
-
-# ---- ray sets --------------------------------------------------------------------------
-def _unit(d):
-    d = np.asarray(d, np.float64)
-    return (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(F32)
-
-
-def aimed_rays():
-    o = np.array([0, 10, 15], np.float64)
-    targets = np.array([(15, 0, -10), (-25, 0, -10), (-5, 0, -10), (-2.5, 0, 10), (-4, 0, -29),
-                        (3, -5.5, 3)], np.float64)
-    d = np.concatenate([_unit(targets - o), np.array([[0, 1, 0]], F32)])
-    return np.tile(o.astype(F32), (len(d), 1)), d
-
-
-AIMED_IDS = [0, 1, 4, 5, 6, 7, -1]
-
-
-def random_rays():
-    rng = np.random.default_rng(1)
-    o = rng.uniform([-30, -5, -35], [20, 15, 20], (1000, 3)).astype(F32)
-    d = _unit(rng.normal(size=(1000, 3)))
-    return o, d
-
-
-def edge_rays():
-    rays = [((0, 10, 15), (0, 0, 0)),
-            ((0, 10, 15), (NAN, 0, -1)),
-            ((0, 0, 15), (0, 0, -1e30)),
-            ((0, 0, 15), (0, 0, -1e-3)),
-            ((0, 0, 15), (0, -1e3, -1e3)),
-            ((1e20, 0, 0), (0, -1, 0)),
-            ((INF, 0, 0), (0, -1, 0)),
-            ((0, -5.5, 0), (1, 0, 0)),
-            ((0, 100, 0), (1, -1e-4, 0))]
-    return (np.array([r[0] for r in rays], F32), np.array([r[1] for r in rays], F32))
-
-
-SETS = {"aimed": aimed_rays, "random": random_rays, "edge": edge_rays}
-
-
-# ---- the oracle, per ray ---------------------------------------------------------------
-_cache = {}
-
-
-def _ukey(u):
-    return bytes(u)
-
-
-def default_u(rm, bounces=0, shadow_mode=0):
-    u = rm.default_uniforms()
-    u.iTime = 1.0
-    u.bounceVar = bounces
-    u.shadow_mode = shadow_mode
-    return u
-
-
-def oracle_march(rm, O, u, o, d, reflected):
-    key = ("march", _ukey(u), o.tobytes(), d.tobytes(), bool(reflected))
-    if key not in _cache:
-        out = np.zeros(len(o), rm.RAY_HIT_DTYPE)
-        for i in range(len(o)):
-            h, _ = O.raymarch(u, o[i], d[i], reflected)
-            out[i]["t"], out[i]["id"], out[i]["material"] = h.hitpoint, h.id, h.material
-            out[i]["albedo"] = tuple(h.color)
-        out.setflags(write=False)
-        _cache[key] = out
-    return _cache[key]
-
-
-def oracle_normals(O, u, o, d, t):
-    n = np.zeros((len(o), 3), F32)
-    for i in np.nonzero(t != F32(-1.0))[0]:
-        with np.errstate(all="ignore"):
-            pos = o[i] + d[i] * t[i]  # float32: a multiply then an add per component
-        assert pos.dtype == F32
-        n[i] = O.get_normal(u, pos)
-    return n
-
-
-def oracle_colors(O, u, o, d):
-    key = ("color", _ukey(u), o.tobytes(), d.tobytes())
-    if key not in _cache:
-        c = np.array([O.render_ray(u, o[i], d[i]) for i in range(len(o))], F32).reshape(len(o), 3)
-        c.setflags(write=False)
-        _cache[key] = c
-    return _cache[key]
-
-
-def bits_equal(a, b, what=""):
-    """Equal as uint32; a NaN counts as equal to a NaN."""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype.itemsize == 4 and b.dtype.itemsize == 4, (what, a.shape, b.shape)
-    ua, ub = a.view(np.uint32), b.view(np.uint32)
-    same = ua == ub
-    if a.dtype.kind == "f" and b.dtype.kind == "f":
-        same |= np.isnan(a) & np.isnan(b)
-    bad = np.argwhere(~same)
-    assert len(bad) == 0, f"{what}: {len(bad)} differ, first at {bad[0]}: {a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}"
-
-
-def hit_fields_equal(got, want, what):
-    for f in ("t", "id", "material", "albedo"):
-        bits_equal(got[f], want[f], f"{what} {f}")
-
-
-def colors_close(got, want, what):
-    got, want = np.asarray(got, F32), np.asarray(want, F32)
-    assert (np.isnan(got) == np.isnan(want)).all(), f"{what}: NaN masks differ"
-    fin = np.isfinite(want)
-    assert (got[~fin & ~np.isnan(want)] == want[~fin & ~np.isnan(want)]).all(), f"{what}: infinities differ"
-    err = np.abs(got[fin].astype(np.float64) - want[fin].astype(np.float64))
-    print(f"{what}: max |colour error| {err.max() if err.size else 0.0:.3g} over {fin.sum()} values")
-    assert (err <= TOL).all(), f"{what}: max error {err.max():.3g} > {TOL}"
-
-
-def zeros(a):
-    return not np.ascontiguousarray(a).view(np.uint32).any()
+AIMED_IDS = [0, 1, 4, 5, 6, 7, -1]  # of records.aimed_rays()
 
 
 @pytest.fixture(scope="module")
@@ -276,16 +155,6 @@ def test_ray_counts(rm, ctx, n):
 
 
 # ---- 7. frame consistency --------------------------------------------------------------
-def pixel_rays(oracle, u, W, H):
-    o, d = np.zeros((H, W, 3), F32), np.zeros((H, W, 3), F32)
-    for py in range(H):
-        for px in range(W):
-            uvx = F32(px * 2 - W) / F32(W)  # glsl:301-305, in float32
-            uvy = F32(py * 2 - H) / F32(H)
-            o[py, px], d[py, px] = oracle.cast_ray(u, float(uvx), float(uvy))
-    return o.reshape(-1, 3), d.reshape(-1, 3)
-
-
 def frame_equals_trace(rm, oracle, r, u, scene=None):
     """The context's own dispatch (RGBA32F) equals a SHADE trace of every pixel's ray."""
     W, H = r.width, r.height
@@ -321,9 +190,6 @@ def test_pick(rm, oracle, ctx):
 
 
 # ---- 9. tables -------------------------------------------------------------------------
-FLAG_SETS = [0, 1, 2, 3, 4, 6, 8]  # every valid combination of the RM_TRACE_* flags
-
-
 def test_default_table_equals_builtin(rm, ctx, gpu):
     u = default_u(rm, 2)
     ro, rd = random_rays()
@@ -349,7 +215,7 @@ def test_default_table_equals_builtin(rm, ctx, gpu):
 
 @pytest.mark.parametrize("which", ["random0", "random1", "random2", "random3", "floor0"])
 def test_tables_against_their_frames_and_the_oracle(rm, oracle, gpu, which):
-    scene = floor_last_scene(rm, 0) if which == "floor0" else random_scene(rm, int(which[-1]))
+    scene = scene_of(rm, which)
     u = rm.sweep_uniforms(60, 120, 1, False, 0)
     W, H = 37, 23
     with rm.Renderer(W, H, outputs=rm.RM_OUT_RGBA32F) as t:

@@ -16,18 +16,13 @@ import pytest
 
 import sdf_model as M
 import table_trace_rays as T
-from test_gpu_sdf import big_scene
-from test_gpu_scene import floor_last_scene, random_scene
-from test_gpu_trace import (FLAG_SETS, INF, SETS, bits_equal, default_u, oracle_colors, oracle_march,
-                            oracle_normals, pixel_rays, zeros)
+from records import (FLAG_SETS, INF, SETS, bits_equal, hit_fields_equal, oracle_colors, oracle_march, oracle_normals,
+                     pixel_rays, records_equal, zeros)
+from scenes import scene_of
+from uniforms import default_u
 
 F32 = np.float32
 FIELDS = ("t", "id", "material", "albedo", "normal", "color")
-
-
-def records_equal(got, want, what):
-    for f in FIELDS:
-        bits_equal(got[f], want[f], f"{what} {f}")
 
 
 def all_rays():
@@ -53,8 +48,7 @@ def test_batch_equals_per_ray(rm, oracle, name, bounces, mode):
             continue
         reflected = bool(flags & rm.RM_TRACE_REFLECTED)
         want = oracle_march(rm, oracle, u, o, d, reflected)
-        for f in ("t", "id", "material", "albedo"):
-            bits_equal(got[f], want[f], f"{what} {f}")
+        hit_fields_equal(got, want, what)
         miss = want["t"] == F32(-1.0)
         assert (got["id"][miss] == -1).all() and (got["material"][miss] == 1.0).all() and zeros(got["albedo"][miss])
         if flags & rm.RM_TRACE_NORMAL:
@@ -89,7 +83,7 @@ def test_default_table_equals_builtin(rm, oracle, itime):
         u.iTime = itime
         for flags in FLAG_SETS:
             records_equal(oracle.trace_rays(u, o, d, flags, scene=rm.default_scene()),
-                          oracle.trace_rays(u, o, d, flags), f"iTime {itime} s{mode} flags {flags}")
+                          oracle.trace_rays(u, o, d, flags), FIELDS, f"iTime {itime} s{mode} flags {flags}")
     for r in (False, True):
         assert (oracle.march_steps(u, o, d, r, scene=rm.default_scene()) == oracle.march_steps(u, o, d, r)).all()
     pts = np.concatenate([M.seeded_points(), M.edge_points()])
@@ -118,10 +112,8 @@ def test_shade_trace_equals_the_frame(rm, oracle, which):
 # ---- 4. tests/sdf_model.py against rmo_sdf_points ---------------------------------------
 @pytest.mark.parametrize("which", ["random0", "random1", "random2", "random3", "floor0", "big30"])
 def test_model_equals_the_oracle_on_tables(rm, oracle, which):
-    scene = (floor_last_scene(rm, 0) if which == "floor0" else big_scene(rm) if which == "big30"
-             else random_scene(rm, int(which[-1])))
-    u = rm.default_uniforms()
-    u.iTime = 1.0
+    scene = scene_of(rm, which)
+    u = default_u(rm)
     pts = np.concatenate([M.seeded_points(), M.edge_points()])
     want = oracle.sdf_points(u, pts, scene, normal=True)
     got = M.sdf_records(rm, scene, 1.0, pts, normal=True)

@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from test_trace_builds import OBJDUMP, _private_sizes
+from code_objects import OBJDUMP, private_sizes
 
 NEW = [("rm_pattern.o", ("9k_patternE", "13k_pattern_oneE")),
        ("rm_table_pattern.o", ("15k_table_patternE", "19k_table_pattern_oneE"))]
@@ -18,7 +18,7 @@ OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
 @pytest.mark.parametrize("obj,kernels", NEW)
 def test_pattern_kernels_use_no_scratch(obj, kernels, tmp_path):
-    priv = _private_sizes(obj, tmp_path)
+    priv = private_sizes(obj, tmp_path)
     assert len(priv) == len(kernels), priv  # the object's only kernels
     for k in kernels:
         assert [name for name in priv if k in name], (k, priv)
@@ -28,5 +28,5 @@ def test_pattern_kernels_use_no_scratch(obj, kernels, tmp_path):
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
 @pytest.mark.parametrize("obj", OLD)
 def test_existing_objects_hold_no_pattern_kernel(obj, tmp_path):
-    priv = _private_sizes(obj, tmp_path)
+    priv = private_sizes(obj, tmp_path)
     assert priv and not [k for k in priv if "pattern" in k], priv

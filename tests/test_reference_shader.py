@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 import glsl_ref as G
-import test_gpu_fuzz_uniforms as fuzz
+import uniforms as fuzz
 
 HERE = os.path.join(os.path.dirname(__file__), "golden")
 META = json.load(open(os.path.join(HERE, "reference_goldens.json")))

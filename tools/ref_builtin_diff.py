@@ -41,7 +41,7 @@ def cases(nfuzz):
             H, W, _ = gold[name + "_rgba32f"].shape
             yield "fixture", name, rm.rm_uniforms.from_buffer_copy(gold[key].tobytes()), W, H
     if nfuzz:
-        import test_gpu_fuzz_uniforms as fuzz
+        import uniforms as fuzz
         for i in range(nfuzz):
             yield "fuzz", f"fuzz{i}", fuzz._uniforms(rm, dict(fuzz.CASES[i], sm=0)), fuzz.W, fuzz.H
 
