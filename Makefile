@@ -59,7 +59,8 @@ $(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
 # round 4).  Both at -O2, which measured 0.4-2 % faster than -O3 for each (round
 # 3, profiles/r03_compiler_ab.txt).  k_sample's object alone takes the lean forms
 # of the once-per-wave and once-per-hit code (-DRM_LEAN_FIXED_WORK=1, DESIGN §4.4
-# item 23; rm_kernels.hip).
+# item 23; rm_kernels.hip) and the downward step loop as a wave-uniform loop
+# (-DRM_FAST_STEPS=1, item 24).
 KFLAGS   := $(HIPFLAGS) -O2 -fno-slp-vectorize
 $(PKG)/build/rm_kernels.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
@@ -67,7 +68,7 @@ $(PKG)/build/rm_kernels.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
 
 $(PKG)/build/rm_kernels_aa.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -c $< -o $@
+	$(HIPCC) $(KFLAGS) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -DRM_FAST_STEPS=1 -c $< -o $@
 
 # the scene-table kernels without SLP vectorisation too (generic -2.7 %, the
 # hiprtc-specialised ones get the same flag in rm_jit.hip: -6.5 % per cfg3 frame)
@@ -202,7 +203,7 @@ $(ASAN_DIR)/rm_kernels.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
 	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -DRM_KERNELS_PIXEL_ONLY -c $< -o $@
 $(ASAN_DIR)/rm_kernels_aa.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
 	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -DRM_FAST_STEPS=1 -c $< -o $@
 $(ASAN_DIR)/rm_host.o: $(CSRC)/rm_host.cpp $(RM_HDRS)
 	@mkdir -p $(dir $@)
 	$(LLVM)/bin/clang++ -std=c++17 -O1 -g -fPIC -ffp-contract=off $(SANFLAGS) -c $< -o $@

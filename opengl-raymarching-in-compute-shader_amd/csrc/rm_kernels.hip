@@ -46,6 +46,23 @@ __device__ unsigned long long* g_wave_times;
 template <bool COUNT>
 constexpr bool kLean = RM_LEAN_FIXED_WORK != 0 && !COUNT;
 
+// The downward step loop as a wave-uniform loop, taken where
+// the build says so, -DRM_FAST_STEPS=1: the supersampled frame kernels' object (Makefile,
+// rm_kernels_aa.o), where it was measured.  On most steps of a march no lane leaves, yet a
+// loop whose exit diverges pays the lane-exit bookkeeping on every step (four scalar
+// instructions that merge the leaving lanes into a mask and write exec).  The step's
+// hit compare is therefore taken as a wave vote, and the steps run in an inner loop
+// whose only exit is scalar: a raised vote, or the segment's last step.  No lane leaves
+// inside it and exec stands.  The lanes' exit code runs once per step on which a lane
+// does leave, with the vote as their mask.  Per lane the float operations, their order
+// and the compares are the plain loop's.
+#ifndef RM_FAST_STEPS
+#define RM_FAST_STEPS 0
+#endif
+constexpr int kStopI = 1 << 20;  // past every step index (nmax <= 512)
+template <bool COUNT>
+constexpr bool kFastSteps = (RM_FAST_STEPS & 1) != 0 && !COUNT;
+
 // RayMarch glsl:125-142 / reflectedRay glsl:144-161.  Returns t or -1.
 // UNIT: a primary ray of a frame whose rays all have |rd| within 2^-20 of 1
 // (Frame::unit_rd, checked on the host): |rd| = 1 serves every bound that
@@ -185,11 +202,31 @@ __device__ float march(const Frame& F, f3 ro, f3 rd, bool reflected, int& id, f3
           // (round 6: one VALU per step fewer, cfg3 -0.5 %, cfg2 -0.5 % per frame,
           // profiles/r06_ab_hadd_cfg*.txt).  At a segment's start d = 0: t + 0 = t.
           float dp = 0.0f;
-          for (int i = ib;; ++i) {
-            t = t + dp;
-            const float d = scene_lazy(ro, rd, t, lc, F.blend, F.omblend);
-            dp = d;
-            if ((d < 0.000001f * t) | (i >= iend)) break;
+          if (kFastSteps<COUNT>) {
+            // The same steps in a wave-uniform inner loop (see kFastSteps).  i advances
+            // with t at the top of the step, so the step that ends the inner loop leaves
+            // it with its own (t, d, i).  The two scalar conditions are one compare: a
+            // raised vote stands for a bound below every step index.
+            for (int i = ib - 1;;) {
+              unsigned long long hitv;
+              asm volatile("");  // keeps the inner loop a loop of its own: merged with the
+                                 // outer one, both back edges get the divergent exit's code
+              for (;;) {
+                t = t + dp;
+                ++i;
+                dp = scene_lazy(ro, rd, t, lc, F.blend, F.omblend);
+                hitv = __builtin_amdgcn_ballot_w64(dp < 0.000001f * t);
+                if (i >= (hitv != 0 ? -kStopI : iend)) break;
+              }
+              if (__builtin_amdgcn_inverse_ballot_w64(hitv) | (i >= iend)) break;
+            }
+          } else {
+            for (int i = ib;; ++i) {
+              t = t + dp;
+              const float d = scene_lazy(ro, rd, t, lc, F.blend, F.omblend);
+              dp = d;
+              if ((d < 0.000001f * t) | (i >= iend)) break;
+            }
           }
           dl = dp;
         } else if (live) {

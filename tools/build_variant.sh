@@ -43,9 +43,11 @@ case "$*" in
   *RM_STATS*) /opt/rocm/bin/hipcc $flags -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" & ;;
   *) lean=-DRM_LEAN_FIXED_WORK=1; case "$*" in *RM_LEAN_FIXED_WORK*) lean=;; esac  # as the Makefile, unless given
      grep -q RM_LEAN_FIXED_WORK "$src/$pkg/csrc/rm_kernels.hip" || lean=
+     fast=-DRM_FAST_STEPS=1; case "$*" in *RM_FAST_STEPS*) fast=;; esac
+     grep -q RM_FAST_STEPS "$src/$pkg/csrc/rm_kernels.hip" || fast=
      pslp=-fno-slp-vectorize; [ -n "$RM_PIXEL_SLP" ] && pslp=-fslp-vectorize
      /opt/rocm/bin/hipcc $flags ${KOPT:--O2} $pslp -DRM_KERNELS_PIXEL_ONLY -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels.o" &
-     /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY $lean -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
+     /opt/rocm/bin/hipcc $flags ${KOPT:--O2} -fno-slp-vectorize -DRM_KERNELS_AA_ONLY $lean $fast -c "$src/$pkg/csrc/rm_kernels.hip" -o "$b/rm_kernels_aa.o" & ;;
 esac
 # the ray-query, G-buffer, SDF-query, adaptive and mesh kernels, as the Makefile builds them
 # (absent in older revisions)

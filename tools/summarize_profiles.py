@@ -29,7 +29,7 @@ def main(src, tag, workload="cfg3", dst="profiles"):
     shutil.copy(os.path.join(src, "trace", "run_kernel_stats.csv"),
                 os.path.join(dst, f"{tag}_kernel_stats.csv"))
     out = {}
-    for sub in ("fetch", "write", "sq", "sq2", "sq3"):
+    for sub in ("fetch", "write", "sq", "sq2", "sq3", "sq4"):
         p = os.path.join(src, sub)
         if not os.path.isdir(p):
             continue
