@@ -4,7 +4,21 @@
 #   make oracle     -> oracle/_build/librm_oracle.so (test infrastructure)
 #   make goldens    -> oracle/_ref/gen_camera_goldens (needs /root/reference; container only)
 #   make glsl_ref   -> oracle/_ref/glsl_ref{,_glm,_ubsan}: the reference's shader as C++ (same condition)
+#   make asan      -> $(PKG)/build/asan/librm.so + oracle/_build/librm_oracle_asan.so (host sanitizers)
 # Built artefacts stay in-tree (git-ignored) so they travel to the GPU box.
+#
+# Every librm is built by the one rule below; a variant (tools/build_variant.sh) and
+# the sanitizer build are that rule with some of these set on the command line:
+#   BUILD=DIR        the object directory (rm_jit_src.inc goes there too)
+#   LIBRM=FILE       the library to link
+#   XFLAGS='-D...'   appended to every compile of librm's objects.  A -DRM_LEAN_FIXED_WORK=
+#                    or -DRM_FAST_STEPS= there replaces rm_kernels_aa.o's default; with
+#                    -DRM_STATS... rm_kernels.hip is compiled once, whole and with the
+#                    plain flags, and rm_kernels_aa.o is left out: the counters must
+#                    live in one code object
+#   KOPT=-O3         the built-in kernels' -O level (default -O2)
+#   RM_PIXEL_SLP=1   rm_kernels.o (k_pixel) with SLP vectorisation, the round-3 flags
+#   SAN=1            the host sanitizer mode (what `make asan` sets)
 
 HIPCC    ?= /opt/rocm/bin/hipcc
 CC       ?= gcc
@@ -19,37 +33,23 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-result
 OFLAGS   := -std=c11 -O3 -ffp-contract=off -fno-fast-math -fopenmp -fPIC -Wall -Wextra
 
+BUILD    := $(PKG)/build
 LIBRM    := $(PKG)/librm.so
 ORACLE   := oracle/_build/librm_oracle.so
 DRIVER   := $(PKG)/rm_frameloop
+XFLAGS   :=
+KOPT     := -O2
+LLVM     ?= /opt/rocm/lib/llvm
 
-# librm's objects, in link order: the link line and the sanitizer build's objects
-# come from this one list.
+# librm's objects, in link order.  Each is compiled from $(CSRC)/NAME.hip (or
+# src_NAME) with $(HIPFLAGS) $(add_NAME) $(XFLAGS); the variables below are all
+# that differs between them.
 RM_OBJS  := rm_api rm_api_comm rm_api_graph rm_frame_math rm_kernels rm_kernels_aa rm_table rm_jit rm_host rm_comm \
             rm_api_trace rm_trace rm_table_trace rm_api_gbuffer rm_gbuffer rm_table_gbuffer \
             rm_api_sdf rm_sdf rm_table_sdf rm_api_adaptive rm_adaptive rm_table_adaptive rm_adaptive_edges \
             rm_api_mesh rm_mesh rm_api_query rm_api_pattern rm_pattern rm_table_pattern \
             rm_adaptive_pattern rm_table_adaptive_pattern
-RM_HDRS  := $(CSRC)/rm_scene.hpp $(CSRC)/rm_shard.hpp $(CSRC)/rm_fastmath.hpp $(CSRC)/rm_internal.hpp $(CSRC)/rm_jit.hpp $(CSRC)/rm_comm.hpp \
-            $(CSRC)/rm_ctx.hpp $(CSRC)/rm_frame_math.hpp $(CSRC)/rm_trace.hpp $(CSRC)/rm_builtin_fast.hpp $(CSRC)/rm_table_lit.hpp $(CSRC)/rm_sdf.hpp $(CSRC)/rm_sdf_args.hpp $(CSRC)/rm_adaptive_args.hpp $(CSRC)/rm_adaptive_tile.hpp \
-            $(CSRC)/rm_mesh_args.hpp $(CSRC)/rm_pattern_args.hpp $(CSRC)/rm_adaptive_pattern.hpp \
-            include/rm_api.h Makefile
-# The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
-# the names they #include each other by.
-JIT_SRCS := rm_table.hip=$(CSRC)/rm_table.hip rm_internal.hpp=$(CSRC)/rm_internal.hpp \
-            rm_scene.hpp=$(CSRC)/rm_scene.hpp rm_shard.hpp=$(CSRC)/rm_shard.hpp \
-            rm_fastmath.hpp=$(CSRC)/rm_fastmath.hpp \
-            ../../include/rm_api.h=include/rm_api.h
-
-.PHONY: all librm oracle driver goldens glsl_ref asan clean
-all: librm oracle driver
-librm: $(LIBRM)
-oracle: $(ORACLE)
-driver: $(DRIVER)
-
-$(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+RM_HDRS  := $(wildcard $(CSRC)/*.hpp) include/rm_api.h Makefile
 
 # rm_kernels.hip is built twice: k_pixel + k_unshard (rm_kernels.o),
 # and k_sample alone (rm_kernels_aa.o), both without SLP vectorisation: pairing
@@ -61,20 +61,20 @@ $(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
 # of the once-per-wave and once-per-hit code (-DRM_LEAN_FIXED_WORK=1, DESIGN §4.4
 # item 23; rm_kernels.hip) and the downward step loop as a wave-uniform loop
 # (-DRM_FAST_STEPS=1, item 24).
-KFLAGS   := $(HIPFLAGS) -O2 -fno-slp-vectorize
-$(PKG)/build/rm_kernels.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -DRM_KERNELS_PIXEL_ONLY -c $< -o $@
-
-$(PKG)/build/rm_kernels_aa.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -DRM_FAST_STEPS=1 -c $< -o $@
+KFLAGS            := $(KOPT) -fno-slp-vectorize
+src_rm_kernels_aa := rm_kernels.hip
+add_rm_kernels    := $(KOPT) $(if $(RM_PIXEL_SLP),-fslp-vectorize,-fno-slp-vectorize) -DRM_KERNELS_PIXEL_ONLY
+add_rm_kernels_aa := $(KFLAGS) -DRM_KERNELS_AA_ONLY \
+                     $(if $(findstring -DRM_LEAN_FIXED_WORK=,$(XFLAGS)),,-DRM_LEAN_FIXED_WORK=1) \
+                     $(if $(findstring -DRM_FAST_STEPS=,$(XFLAGS)),,-DRM_FAST_STEPS=1)
+ifneq ($(findstring -DRM_STATS,$(XFLAGS)),)
+RM_OBJS           := $(filter-out rm_kernels_aa,$(RM_OBJS))
+add_rm_kernels    :=
+endif
 
 # the scene-table kernels without SLP vectorisation too (generic -2.7 %, the
 # hiprtc-specialised ones get the same flag in rm_jit.hip: -6.5 % per cfg3 frame)
-$(PKG)/build/rm_table.o: $(CSRC)/rm_table.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+add_rm_table      := -fno-slp-vectorize
 
 # The query and output families in objects of their own, so
 # that rm_kernels.o / rm_kernels_aa.o / rm_table.o are what they are without
@@ -84,10 +84,7 @@ $(PKG)/build/rm_table.o: $(CSRC)/rm_table.hip $(RM_HDRS)
 # (the geometry-edge classifier, mesh extraction) take the same flags.
 BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive rm_pattern rm_adaptive_pattern
 PLAIN_FAMS   := rm_adaptive_edges rm_mesh
-$(BUILTIN_FAMS:%=$(PKG)/build/%.o): $(CSRC)/rm_kernels.hip
-$(BUILTIN_FAMS:%=$(PKG)/build/%.o) $(PLAIN_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(KFLAGS) -c $< -o $@
+$(foreach o,$(BUILTIN_FAMS) $(PLAIN_FAMS),$(eval add_$o := $(KFLAGS)))
 
 # The scene-table halves include rm_table.hip in the same way, with rm_table.o's
 # flags and one more: k_table_trace holds the table march twice over (the fast
@@ -98,29 +95,48 @@ $(BUILTIN_FAMS:%=$(PKG)/build/%.o) $(PLAIN_FAMS:%=$(PKG)/build/%.o): $(PKG)/buil
 TRACE_INLINE := -mllvm -amdgpu-inline-max-bb=8000
 TABLE_FAMS   := rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern \
                 rm_table_adaptive_pattern
-$(TABLE_FAMS:%=$(PKG)/build/%.o): $(PKG)/build/%.o: $(CSRC)/%.hip $(CSRC)/rm_table.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(TRACE_INLINE) -c $< -o $@
+$(foreach o,$(TABLE_FAMS),$(eval add_$o := $(add_rm_table) $(TRACE_INLINE)))
 
-$(PKG)/build/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
+# The objects that hold kernels, each kernel in one of them (tests/test_build_recipe.py).
+RM_KERNEL_OBJS := $(filter rm_kernels rm_kernels_aa rm_table $(BUILTIN_FAMS) $(PLAIN_FAMS) $(TABLE_FAMS),$(RM_OBJS))
+
+# The table kernel's sources, embedded in librm.so for hiprtc (rm_jit.hip), under
+# the names they #include each other by.
+JIT_SRCS := rm_table.hip=$(CSRC)/rm_table.hip rm_internal.hpp=$(CSRC)/rm_internal.hpp \
+            rm_scene.hpp=$(CSRC)/rm_scene.hpp rm_shard.hpp=$(CSRC)/rm_shard.hpp \
+            rm_fastmath.hpp=$(CSRC)/rm_fastmath.hpp \
+            ../../include/rm_api.h=include/rm_api.h
+add_rm_jit  := -I$(BUILD)
+
+src_rm_host := rm_host.cpp
+add_rm_host := -x c++
+# RCCL is bound at run time (dlopen, rm_comm.cpp): librm does not link it.
+src_rm_comm := rm_comm.cpp
+add_rm_comm := -x hip
+
+compile = $(HIPCC) $(HIPFLAGS) $(add_$*) $(XFLAGS)
+link    = $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
+
+.PHONY: all librm oracle driver goldens glsl_ref asan clean
+all: librm oracle driver
+librm: $(LIBRM)
+oracle: $(ORACLE)
+driver: $(DRIVER)
+
+.SECONDEXPANSION:
+$(RM_OBJS:%=$(BUILD)/%.o): $(BUILD)/%.o: $(CSRC)/$$(or $$(src_$$*),$$*.hip) $(RM_HDRS)
+	@mkdir -p $(dir $@)
+	$(or $(compile_$*),$(compile)) -c $< -o $@
+$(BUILTIN_FAMS:%=$(BUILD)/%.o): $(CSRC)/rm_kernels.hip
+$(TABLE_FAMS:%=$(BUILD)/%.o): $(CSRC)/rm_table.hip
+$(BUILD)/rm_jit.o: $(BUILD)/rm_jit_src.inc
+
+$(BUILD)/rm_jit_src.inc: $(CSRC)/rm_table.hip $(RM_HDRS) $(PKG)/tools/embed_sources.py
 	@mkdir -p $(dir $@)
 	python3 $(PKG)/tools/embed_sources.py $@ $(JIT_SRCS)
 
-$(PKG)/build/rm_jit.o: $(CSRC)/rm_jit.hip $(RM_HDRS) $(PKG)/build/rm_jit_src.inc
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -I$(PKG)/build -c $< -o $@
-
-$(PKG)/build/rm_host.o: $(CSRC)/rm_host.cpp $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
-
-# RCCL is bound at run time (dlopen, rm_comm.cpp): librm does not link it.
-$(PKG)/build/rm_comm.o: $(CSRC)/rm_comm.cpp $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
-
-$(LIBRM): $(RM_OBJS:%=$(PKG)/build/%.o)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lhiprtc -ldl
+$(LIBRM): $(RM_OBJS:%=$(BUILD)/%.o)
+	$(link)
 
 $(ORACLE): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
 	@mkdir -p $(dir $@)
@@ -177,42 +193,27 @@ oracle/_ref/glsl_ref_ubsan: $(GLSL_DEPS)
 # ---- host sanitizer build: CPU suite under ASan + UBSan ---------
 # librm's host code (the C-ABI, the table compiler and its bounds, the uniform
 # lookup, input replay, the shard map, the hiprtc driver) and the oracle, built
-# with AddressSanitizer + UndefinedBehaviorSanitizer, every report fatal.  The
-# sanitizers are on the host side only (-Xarch_host; the device code is the
-# production build's): this build is for the CPU container, where no kernel runs
-# anyway (GPU sanitizers are not available).  tests/test_sanitizers.py runs the
-# host-logic CPU tests against it (LD_PRELOAD of clang's ASan runtime, RM_LIBRM,
-# RM_ORACLE).
-LLVM     ?= /opt/rocm/lib/llvm
-ASAN_DIR := $(PKG)/build/asan
-ASANLIB  := $(ASAN_DIR)/librm.so
-ASANORC  := oracle/_build/librm_oracle_asan.so
-SANHOST  := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
-            -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer
+# with AddressSanitizer + UndefinedBehaviorSanitizer, every report fatal.  This
+# build is for the CPU container, where no kernel runs anyway (GPU sanitizers are
+# not available).  tests/test_sanitizers.py runs the host-logic CPU tests against
+# it (LD_PRELOAD of clang's ASan runtime, RM_LIBRM, RM_ORACLE).
+# librm is the rule above with SAN=1, in a directory of its own: the same objects
+# from the same sources with the same defines, -O1 -g and the sanitizers on the
+# host side (-Xarch_host) after each object's own flags; rm_host.cpp, which has no
+# device side, through clang++; the link through clang++ with the shared runtime.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer
-ASAN_OBJS := $(RM_OBJS:%=$(ASAN_DIR)/%.o)
-asan: $(ASANLIB) $(ASANORC)
+ifdef SAN
+compile  += -O1 -g -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+            -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer
+compile_rm_host := $(LLVM)/bin/clang++ -std=c++17 -O1 -g -fPIC -ffp-contract=off $(SANFLAGS)
+link      = $(LLVM)/bin/clang++ -shared -fPIC $(SANFLAGS) -shared-libsan -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lhiprtc -ldl \
+            -Wl,-rpath,/opt/rocm/lib
+endif
+ASAN_DIR := $(PKG)/build/asan
+ASANORC  := oracle/_build/librm_oracle_asan.so
+asan: $(ASANORC)
+	+$(MAKE) SAN=1 BUILD=$(ASAN_DIR) LIBRM=$(ASAN_DIR)/librm.so librm
 
-$(BUILTIN_FAMS:%=$(ASAN_DIR)/%.o): $(CSRC)/rm_kernels.hip
-$(TABLE_FAMS:%=$(ASAN_DIR)/%.o): $(CSRC)/rm_table.hip
-$(ASAN_DIR)/%.o: $(CSRC)/%.hip $(RM_HDRS) $(PKG)/build/rm_jit_src.inc
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -I$(PKG)/build -c $< -o $@
-$(ASAN_DIR)/rm_kernels.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -DRM_KERNELS_PIXEL_ONLY -c $< -o $@
-$(ASAN_DIR)/rm_kernels_aa.o: $(CSRC)/rm_kernels.hip $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -DRM_KERNELS_AA_ONLY -DRM_LEAN_FIXED_WORK=1 -DRM_FAST_STEPS=1 -c $< -o $@
-$(ASAN_DIR)/rm_host.o: $(CSRC)/rm_host.cpp $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(LLVM)/bin/clang++ -std=c++17 -O1 -g -fPIC -ffp-contract=off $(SANFLAGS) -c $< -o $@
-$(ASAN_DIR)/rm_comm.o: $(CSRC)/rm_comm.cpp $(RM_HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -O1 -g $(SANHOST) -x hip -c $< -o $@
-$(ASANLIB): $(ASAN_OBJS)
-	$(LLVM)/bin/clang++ -shared -fPIC $(SANFLAGS) -shared-libsan -o $@ $^ -L/opt/rocm/lib -lamdhip64 -lhiprtc -ldl \
-	  -Wl,-rpath,/opt/rocm/lib
 $(ASANORC): oracle/rm_oracle.c oracle/rm_oracle.h include/rm_api.h
 	@mkdir -p $(dir $@)
 	$(LLVM)/bin/clang -std=c11 -O1 -g -ffp-contract=off -fno-fast-math -fopenmp -fPIC -Wall $(SANFLAGS) \

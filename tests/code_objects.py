@@ -1,6 +1,8 @@
-"""The gfx950 code object of a built object file, and the kernel descriptors of an AMDGPU
-ELF: the one extractor and the one parser the *_builds.py tests, test_scene_table.py and
-tools/co_diff.py share.  Plain helpers, no fixtures."""
+"""The gfx950 code object of a built object file, the kernel descriptors of an AMDGPU
+ELF, and what the Makefile says of the build (its flags, its objects): the one extractor,
+the one parser and the one place that asks make, shared by the *_builds.py tests,
+test_build_recipe.py, test_scene_table.py and tools/co_diff.py.  Plain helpers, no
+fixtures."""
 import os
 import shutil
 import struct
@@ -9,6 +11,26 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "build")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+
+
+def make_words(var):
+    """The words of the Makefile's variable `var`, as make expands it."""
+    r = subprocess.run(["make", "-s", "--no-print-directory", "--eval", f"print-var: ; @echo $({var})", "print-var"],
+                       cwd=ROOT, capture_output=True, text=True, check=True)
+    return r.stdout.split()
+
+
+def hipflags():
+    """The Makefile's HIPFLAGS, the flags every object of librm is compiled with."""
+    flags = make_words("HIPFLAGS")
+    assert "-ffp-contract=off" in flags, flags
+    return flags
+
+
+def kernel_objects(but=()):
+    """The objects of librm that hold kernels (the Makefile's RM_KERNEL_OBJS, which
+    test_build_recipe.py holds against the build), as file names, except those in `but`."""
+    return [o + ".o" for o in make_words("RM_KERNEL_OBJS") if o + ".o" not in but]
 
 
 def gfx950_code_object(obj_path, work_dir):

@@ -7,13 +7,16 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, private_sizes
+from code_objects import OBJDUMP, kernel_objects, private_sizes
 
 NEW = [("rm_adaptive.o", ("16k_adapt_classifyE", "12k_adapt_maskE", "12k_adapt_scanE", "15k_adapt_scatterE",
                           "14k_adapt_refineE")),
        ("rm_table_adaptive.o", ("20k_table_adapt_refineE",))]
-OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
-       "rm_table_gbuffer.o", "rm_sdf.o", "rm_table_sdf.o"]
+# every other object that holds kernels, except the later members of the family, whose
+# kernels are k_adapt_* too: the geometry-edge classifier (test_adaptive_edges_builds.py) and
+# pattern refinement (test_adaptive_pattern_builds.py)
+OLD = kernel_objects(but=[obj for obj, _ in NEW] + ["rm_adaptive_edges.o", "rm_adaptive_pattern.o",
+                                                    "rm_table_adaptive_pattern.o"])
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")

@@ -6,11 +6,10 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, private_sizes
+from code_objects import OBJDUMP, kernel_objects, private_sizes
 
 KERNEL = "22k_adapt_classify_edges"
-OTHERS = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
-          "rm_table_gbuffer.o", "rm_sdf.o", "rm_table_sdf.o", "rm_adaptive.o", "rm_table_adaptive.o"]
+OTHERS = kernel_objects(but=["rm_adaptive_edges.o"])
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")

@@ -10,13 +10,11 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, built_descriptors
+from code_objects import OBJDUMP, built_descriptors, kernel_objects
 
 NEW = {"rm_adaptive_pattern.o": ("22k_adapt_refine_patternE", "26k_adapt_refine_pattern_oneE"),
        "rm_table_adaptive_pattern.o": ("28k_table_adapt_refine_patternE", "32k_table_adapt_refine_pattern_oneE")}
-OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
-       "rm_table_gbuffer.o", "rm_sdf.o", "rm_table_sdf.o", "rm_adaptive.o", "rm_table_adaptive.o",
-       "rm_adaptive_edges.o", "rm_mesh.o", "rm_pattern.o", "rm_table_pattern.o"]
+OLD = kernel_objects(but=list(NEW))
 
 pytestmark = pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
 

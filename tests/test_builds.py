@@ -10,7 +10,7 @@ import subprocess
 
 import pytest
 
-from code_objects import OBJDUMP, built_descriptors, field
+from code_objects import OBJDUMP, built_descriptors, field, hipflags
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "csrc")
@@ -29,8 +29,7 @@ SOURCE = {"table_dbl_probes": "rm_table.hip"}
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("name", sorted(DIAG))
 def test_diagnostic_build_compiles(name, tmp_path):
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-           "--cuda-device-only", "-c", os.path.join(CSRC, SOURCE.get(name, "rm_kernels.hip")),
+    cmd = [HIPCC, *hipflags(), "--cuda-device-only", "-c", os.path.join(CSRC, SOURCE.get(name, "rm_kernels.hip")),
            "-o", str(tmp_path / "k.o")] + DIAG[name]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]

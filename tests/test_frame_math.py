@@ -15,25 +15,19 @@ import subprocess
 
 import pytest
 
+from code_objects import hipflags
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opengl-raymarching-in-compute-shader_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 ORACLE_DIR = os.path.join(ROOT, "oracle", "_build")
 
 
-def _hipflags():
-    r = subprocess.run(["make", "-s", "--no-print-directory", "--eval", "print-hipflags: ; @echo $(HIPFLAGS)",
-                        "print-hipflags"], cwd=ROOT, capture_output=True, text=True, check=True)
-    flags = r.stdout.split()
-    assert "-ffp-contract=off" in flags, flags
-    return flags
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_step0_is_the_oracles_sdf_at_the_camera(tmp_path):
     if not os.path.exists(os.path.join(ORACLE_DIR, "librm_oracle.so")):
         pytest.skip("oracle not built")
-    flags = _hipflags()
+    flags = hipflags()
     objs = []
     for src, extra in ((os.path.join(ROOT, "tests", "frame_math_main.cpp"), []),
                        (os.path.join(CSRC, "rm_frame_math.hip"), []),

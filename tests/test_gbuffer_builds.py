@@ -7,11 +7,11 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, private_sizes
+from code_objects import OBJDUMP, kernel_objects, private_sizes
 
 NEW = [("rm_gbuffer.o", ("12k_gbuf_pixelE", "13k_gbuf_sampleE")),
        ("rm_table_gbuffer.o", ("18k_table_gbuf_pixelE", "19k_table_gbuf_sampleE"))]
-OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o"]
+OLD = kernel_objects(but=[obj for obj, _ in NEW])
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")

@@ -6,13 +6,13 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, private_sizes
+from code_objects import OBJDUMP, kernel_objects, private_sizes
 
 NEW = [("rm_pattern.o", ("9k_patternE", "13k_pattern_oneE")),
        ("rm_table_pattern.o", ("15k_table_patternE", "19k_table_pattern_oneE"))]
-OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
-       "rm_table_gbuffer.o", "rm_sdf.o", "rm_table_sdf.o", "rm_adaptive.o", "rm_table_adaptive.o",
-       "rm_adaptive_edges.o", "rm_mesh.o"]
+# every other object that holds kernels, except pattern refinement's, whose kernels are
+# k_*_refine_pattern* (test_adaptive_pattern_builds.py)
+OLD = kernel_objects(but=[obj for obj, _ in NEW] + ["rm_adaptive_pattern.o", "rm_table_adaptive_pattern.o"])
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")

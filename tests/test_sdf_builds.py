@@ -7,12 +7,11 @@ import os
 
 import pytest
 
-from code_objects import OBJDUMP, private_sizes
+from code_objects import OBJDUMP, kernel_objects, private_sizes
 
 NEW = [("rm_sdf.o", ("12k_sdf_pointsE", "10k_sdf_gridE")),
        ("rm_table_sdf.o", ("18k_table_sdf_pointsE", "16k_table_sdf_gridE"))]
-OLD = ["rm_kernels.o", "rm_kernels_aa.o", "rm_table.o", "rm_trace.o", "rm_table_trace.o", "rm_gbuffer.o",
-       "rm_table_gbuffer.o"]
+OLD = kernel_objects(but=[obj for obj, _ in NEW])
 
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump not installed")
