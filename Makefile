@@ -48,7 +48,7 @@ RM_OBJS  := rm_api rm_api_comm rm_api_graph rm_frame_math rm_kernels rm_kernels_
             rm_api_trace rm_trace rm_table_trace rm_api_gbuffer rm_gbuffer rm_table_gbuffer \
             rm_api_sdf rm_sdf rm_table_sdf rm_api_adaptive rm_adaptive rm_table_adaptive rm_adaptive_edges \
             rm_api_mesh rm_mesh rm_api_query rm_api_pattern rm_pattern rm_table_pattern \
-            rm_adaptive_pattern rm_table_adaptive_pattern
+            rm_adaptive_pattern rm_table_adaptive_pattern rm_api_accum rm_accum rm_table_accum
 RM_HDRS  := $(wildcard $(CSRC)/*.hpp) include/rm_api.h Makefile
 
 # rm_kernels.hip is built twice: k_pixel + k_unshard (rm_kernels.o),
@@ -76,13 +76,13 @@ endif
 # hiprtc-specialised ones get the same flag in rm_jit.hip: -6.5 % per cfg3 frame)
 add_rm_table      := -fno-slp-vectorize
 
-# The query and output families (DESIGN §4.9-§4.15) in objects of their own, so
+# The query and output families (DESIGN §4.9-§4.16) in objects of their own, so
 # that rm_kernels.o / rm_kernels_aa.o / rm_table.o are what they are without
 # them.  The built-in scene's (ray queries, the G-buffer frame kernels, SDF field
-# queries, adaptive supersampling, sample-pattern frames, pattern refinement) include the render kernels' source for its
+# queries, adaptive supersampling, sample-pattern frames, pattern refinement, accumulation) include the render kernels' source for its
 # device code alone and take that source's flags; the scene-independent ones
 # (the geometry-edge classifier, mesh extraction) take the same flags.
-BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive rm_pattern rm_adaptive_pattern
+BUILTIN_FAMS := rm_trace rm_gbuffer rm_sdf rm_adaptive rm_pattern rm_adaptive_pattern rm_accum
 PLAIN_FAMS   := rm_adaptive_edges rm_mesh
 $(foreach o,$(BUILTIN_FAMS) $(PLAIN_FAMS),$(eval add_$o := $(KFLAGS)))
 
@@ -94,7 +94,7 @@ $(foreach o,$(BUILTIN_FAMS) $(PLAIN_FAMS),$(eval add_$o := $(KFLAGS)))
 # raised).
 TRACE_INLINE := -mllvm -amdgpu-inline-max-bb=8000
 TABLE_FAMS   := rm_table_trace rm_table_gbuffer rm_table_sdf rm_table_adaptive rm_table_pattern \
-                rm_table_adaptive_pattern
+                rm_table_adaptive_pattern rm_table_accum
 $(foreach o,$(TABLE_FAMS),$(eval add_$o := $(add_rm_table) $(TRACE_INLINE)))
 
 # The objects that hold kernels, each kernel in one of them (tests/test_build_recipe.py).

@@ -83,6 +83,25 @@ inline int dispatchPattern(rm_ctx* p, int preset = RM_PATTERN_GRID2) {
   return rc != RM_OK ? rc : rm_dispatch_pattern(p, &s);
 }
 inline int dispatchPattern(rm_ctx* p, const rm_sample_pattern& pattern) { return rm_dispatch_pattern(p, &pattern); }
+// the pattern's samples added onto the context's sum, the frame their running mean
+// (rm_dispatch_accumulate); `samples` more Halton points per pixel in calls of up to
+// RM_MAX_SAMPLES, continuing the sequence at the context's sample count
+inline int dispatchAccumulate(rm_ctx* p, const rm_sample_pattern& pattern, bool restart = false) {
+  return rm_dispatch_accumulate(p, &pattern, restart ? RM_ACCUM_RESTART : 0u);
+}
+inline int dispatchAccumulate(rm_ctx* p, int samples) {
+  for (int done = 0; done < samples;) {
+    int64_t first = 0;
+    rm_sample_pattern s;
+    const int n = samples - done < RM_MAX_SAMPLES ? samples - done : RM_MAX_SAMPLES;
+    int rc = rm_accum_samples(p, &first);
+    if (rc == RM_OK) rc = rm_sample_pattern_halton(&s, first, n);
+    if (rc == RM_OK) rc = rm_dispatch_accumulate(p, &s, 0u);
+    if (rc != RM_OK) return rc;
+    done += n;
+  }
+  return RM_OK;
+}
 // dispatchAdaptiveEdges with a preset pattern's samples on the flagged pixels
 // (rm_dispatch_adaptive_pattern; the default, GRID4: sixteen centred samples on the edges)
 inline int dispatchAdaptivePattern(rm_ctx* p, int preset = RM_PATTERN_GRID4, const rm_aa_criteria* criteria = nullptr) {

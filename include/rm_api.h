@@ -785,8 +785,8 @@ int rm_dispatch_adaptive_edges(rm_ctx *ctx, const rm_aa_criteria *criteria);
  * per pixel at the offsets of an rm_sample_pattern, in pixels from the AA-off
  * frame's ray (the ray rm_pick casts), and stores their mean: a re-centred or
  * rotated grid that registers with the AA-off frame and the G-buffer, 8, 9 or 16
- * samples per pixel, or one jittered sample per frame (n = 1) for a caller's own
- * temporal accumulation.
+ * samples per pixel, or one jittered sample per frame (n = 1) for temporal
+ * accumulation (rm_dispatch_accumulate below keeps the sum).
  *
  * The rule.  Every operation is one IEEE single-precision operation in the order
  * written, with no FMA.
@@ -821,9 +821,9 @@ int rm_dispatch_adaptive_edges(rm_ctx *ctx, const rm_aa_criteria *criteria);
  *    rm_set_scene tables (with rm_scene_specialize on the generic table code
  *    renders, as the adaptive refinement does: same values).  RM_ERR_STATE on a
  *    context with counters, nshards > 1, a communicator, ngpus >= 1,
- *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay, no
- *    accumulation across calls.  (Pattern refinement in the adaptive calls: the
- *    next section.) */
+ *    RM_OUT_GBUFFER or rm_graph_enable on; no batches, no graph replay.
+ *    (Pattern refinement in the adaptive calls: the next section.  A sum kept
+ *    across calls: progressive accumulation, the section after it.) */
 #define RM_HAS_SAMPLE_PATTERN 1
 #define RM_MAX_SAMPLES 16
 #define RM_PATTERN_CUMULATIVE 1u      /* flags: offsets are increments, the GLSL's x += o / W */
@@ -895,7 +895,8 @@ int rm_dispatch_pattern(rm_ctx *ctx, const rm_sample_pattern *p);
  *    min(ceil(W H / 64), 128 x compute units) workgroups.
  *  - Out of scope in this version: batches, graph replay, shards,
  *    hiprtc-specialised refine kernels (the generic table code refines, same
- *    values), accumulation across calls. */
+ *    values), accumulation across calls in these calls (rm_dispatch_accumulate
+ *    sums whole pattern frames; a refined pixel would need a count of its own). */
 #define RM_HAS_ADAPTIVE_PATTERN 1
 /* rm_dispatch_adaptive_edges with `pattern`'s samples on the flagged pixels.  Asynchronous. */
 int rm_dispatch_adaptive_pattern(rm_ctx *ctx, const rm_aa_criteria *criteria, const rm_sample_pattern *pattern);
@@ -904,6 +905,116 @@ int rm_dispatch_adaptive_pattern(rm_ctx *ctx, const rm_aa_criteria *criteria, co
 int rm_dispatch_refine_pattern(rm_ctx *ctx, const uint8_t *mask, size_t row_pitch, const rm_sample_pattern *pattern);
 int rm_dispatch_refine_pattern_device(rm_ctx *ctx, const void *mask_dev, size_t row_pitch,
                                       const rm_sample_pattern *pattern);
+
+/* ---- progressive accumulation: sample sums kept across dispatches -----------------
+ * An extension to the sample patterns.  rm_dispatch_accumulate renders a pattern's
+ * samples and adds them onto a sum the context keeps, so that a frame is the mean
+ * of every sample since the sum was last restarted: more than RM_MAX_SAMPLES
+ * samples per pixel for a converging still image, and, with a uniform changed
+ * between calls, soft shadows from a moved light, motion blur over iTime or depth
+ * of field from a moved camera.
+ *
+ * The rule.  A context gets two new pieces of state.
+ *
+ *  - The sum image.  [height][width] float4, 16-byte aligned.  It is allocated on
+ *    the first accumulating call.
+ *  - A host-side sample count N.  int64, 0 after rm_create.
+ *
+ * rm_dispatch_accumulate(ctx, pattern, flags) renders the pattern's n samples of
+ * every pixel exactly as rm_dispatch_pattern does.  The uv comes from
+ * rm_pattern_uv_table.  c_s is the SHADE trace of that ray.  The call uses the
+ * context's current uniforms and scene.  Then, per pixel and per channel, it
+ * performs these steps.  Each one is a single IEEE single-precision operation in
+ * this order, with no FMA.
+ *
+ *  - If N == 0:
+ *     - S = c_0;
+ *     - then S = S + c_s for s = 1..n-1.
+ *  - Otherwise S = S + c_s for s = 0..n-1.
+ *     - The stored sum is added first, then the samples in pattern order.
+ *  - N = N + n.
+ *  - out = S / (float)N, alpha 1.0f.
+ *     - RGBA8 is the usual quantisation of out.
+ *     - (float)N is the int64-to-float conversion, round to nearest even.  It is
+ *       formed on the host.
+ *  - The sum image's pixel becomes (S.r, S.g, S.b, (float)N).
+ *     - A caller's own shader can therefore resolve it as rgb / w.
+ *
+ * Three anchors follow from the rule, and the tests rest on them.
+ *
+ *  1. With N == 0, one call gives the rm_dispatch_pattern(pattern) frame bit for
+ *     bit.
+ *     - S = c_0, not 0 + c_0, so a -0.0f sample stays -0.0f.
+ *  2. Take calls with absolute (non-cumulative) patterns p1, p2, ... whose
+ *     concatenation is a valid pattern p (total <= 16).  They give the
+ *     rm_dispatch_pattern(p) frame bit for bit.
+ *     - This holds however the samples are split, including sixteen n = 1 calls.
+ *  3. Past 16 samples the frame is a numpy float32 running sum of SHADE traces,
+ *     taken in call order and then sample order.
+ *
+ * Nothing resets the sum but the caller.
+ *
+ *  - The uniforms and the scene may change between calls, and each call adds what
+ *    it renders under them.
+ *  - This is how motion blur, lens blur and area lights are obtained, and it is
+ *    documented behaviour, not an accident.
+ *  - The sum is touched only by rm_dispatch_accumulate and rm_accum_reset.
+ *     - rm_dispatch, rm_dispatch_frames, rm_dispatch_pattern and the adaptive calls
+ *       overwrite the colour images as always and leave S and N alone.
+ *     - The next accumulating call continues and rewrites the colour images from
+ *       S / N.
+ *  - Every accumulating call reads the sum the one before it wrote, on the
+ *    context's stream.  rm_set_stream waits only when it leaves the context's
+ *    own stream: a caller who moves the context from one stream of theirs to
+ *    another (or back to its own) between accumulating calls orders the new
+ *    stream behind the old one first, for example with rm_wait_output on the
+ *    new stream before rm_set_stream.
+ *
+ * Contexts and errors of rm_dispatch_accumulate are rm_dispatch_pattern's:
+ * RM_ERR_STATE, naming the call, on a context with counters, nshards > 1, a
+ * communicator, ngpus >= 1, RM_OUT_GBUFFER or rm_graph_enable on; RM_ERR_INVALID
+ * for a null context or pattern (nothing is touched), for an invalid pattern (the
+ * sample patterns' validation, the reason in rm_last_error after the call's name)
+ * and for an unknown flag bit.  A call that fails leaves S and N as they were.
+ * Afterwards the context reads as after rm_dispatch_pattern (the readbacks,
+ * rm_get_output_rgba8 / rm_set_output_rgba8, rm_wait_output, rm_set_stream,
+ * rm_synchronize); u.AA is ignored and the uniforms stay; with rm_enable_timing the
+ * call is one bracketed launch; the pattern's uv table is the one
+ * rm_dispatch_pattern and the pattern refinements share, so a repeated pattern
+ * uploads nothing.  The built-in scene and rm_set_scene tables are served; with
+ * rm_scene_specialize on the generic table code renders, with the same values.
+ *
+ * Out of scope in this version: accumulation in the adaptive and refine calls (it
+ * needs per-pixel counts; the w channel is where they would go), batches, graph
+ * replay, shards and G-buffer contexts, a hiprtc-specialised accumulation kernel,
+ * exponential blends and per-sample weights, variance or convergence estimates,
+ * loading a saved sum back into a context. */
+#define RM_HAS_ACCUMULATION 1
+#define RM_ACCUM_RESTART 1u   /* flags: N = 0 first, so the call's samples replace the sum */
+/* The pattern's samples added onto the sum, and the frame S / N.  Asynchronous. */
+int rm_dispatch_accumulate(rm_ctx *ctx, const rm_sample_pattern *pattern, uint32_t flags);
+/* N = 0; no device work; the old sum is never read again.  RM_ERR_INVALID for a null context. */
+int rm_accum_reset(rm_ctx *ctx);
+/* N; no synchronisation.  RM_ERR_INVALID for a null context or output (nothing written). */
+int rm_accum_samples(const rm_ctx *ctx, int64_t *samples);
+/* The sum image, by the layout rules of rm_read_rgba32f (row_pitch in bytes, 0 = a
+ * row; flip_y).  Synchronous.  RM_ERR_STATE while N == 0. */
+int rm_read_accum(rm_ctx *ctx, float *dst, size_t row_pitch, int flip_y);
+/* The sum image on the device, allocated on first use, whatever N is; its contents
+ * are undefined while N == 0.  Order reads after the context's stream
+ * (rm_wait_output).  RM_ERR_STATE on the contexts rm_dispatch_accumulate refuses. */
+int rm_get_accum(rm_ctx *ctx, void **device_ptr);
+/* A pattern of n points of the Halton sequence in bases 2 and 3, re-centred on the
+ * pixel, so that callers do not each invent a sequence: struct_size, flags = 0, n,
+ * the entries past n zero, and for sample s, with index i = first + s + 1,
+ *   dx[s] = (float)(R(i, 2) - 0.5),  dy[s] = (float)(R(i, 3) - 0.5).
+ * R(i, b) is computed in double, each operation one IEEE double operation in the
+ * order written:
+ *   f = 1.0 / b; r = 0.0; while (i > 0) { r = r + (double)(i % b) * f; i = i / b; f = f / (double)b; }
+ * (the product and the sum are separate operations).  Pure host: no context, no
+ * device.  RM_ERR_INVALID, with nothing written, for NULL, n outside
+ * 1..RM_MAX_SAMPLES or first outside 0..2^40. */
+int rm_sample_pattern_halton(rm_sample_pattern *p, int64_t first, int32_t n);
 
 /* ---- one rank per process: RCCL-gathered frames -------------
  * The multi-process form of rm_config.ngpus, for hosts that run one process

@@ -166,10 +166,10 @@ RenderKernel rm::pick_kernel(const rm_ctx* c, const rmd::Frame& F) {
 // frames only).
 const SceneKernels& rm::scene_kernels(const rm_ctx* c) {
   static const SceneKernels builtin{launch_trace, launch_sdf_points, launch_sdf_grid, launch_adapt_refine,
-                                    launch_pattern, launch_adapt_refine_pattern};
+                                    launch_pattern, launch_adapt_refine_pattern, launch_accum};
   static const SceneKernels table{launch_table_trace, launch_table_sdf_points, launch_table_sdf_grid,
                                   launch_table_adapt_refine, launch_table_pattern,
-                                  launch_table_adapt_refine_pattern};
+                                  launch_table_adapt_refine_pattern, launch_table_accum};
   return c->nprims ? table : builtin;
 }
 
@@ -201,7 +201,8 @@ void free_all(rm_ctx* c) {
   for (void** p : {(void**)&c->d_gathered, (void**)&c->d_frame, (void**)&c->d_gathered32, (void**)&c->d_frame32,
                    (void**)&c->d_rgba8, (void**)&c->d_rgba32f, &c->d_gbuf, (void**)&c->d_counts, (void**)&c->d_counters,
                    (void**)&c->d_uv, (void**)&c->d_scene, (void**)&c->d_aa_mask, (void**)&c->d_aa_list,
-                   (void**)&c->d_aa_counts, (void**)&c->d_aa_offsets, (void**)&c->d_aa_total}) {
+                   (void**)&c->d_aa_counts, (void**)&c->d_aa_offsets, (void**)&c->d_aa_total,
+                   (void**)&c->d_accum}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -211,6 +212,7 @@ void free_all(rm_ctx* c) {
     *b = DevBuf();
   }
   c->aa_dispatched = false;
+  c->accum_n = 0;
   c->pat.n = 0;
   if (c->pat_ev) {
     if (c->pat_ev_pending) (void)hipEventSynchronize(c->pat_ev);

@@ -3,7 +3,8 @@
 // rm_api_comm.hip (RCCL-gathered frames), rm_api_graph.hip (hipGraph replay),
 // rm_api_trace.hip (ray queries), rm_api_gbuffer.hip (the G-buffer image),
 // rm_api_sdf.hip (SDF field queries), rm_api_adaptive.hip (adaptive supersampling),
-// rm_api_pattern.hip (sample-pattern frames and the pattern's table), rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
+// rm_api_pattern.hip (sample-pattern frames and the pattern's table), rm_api_accum.hip
+// (progressive accumulation), rm_api_mesh.hip (SDF mesh extraction) and rm_api_query.hip (what the three query
 // families share: their frame constants, checks and staging buffers).
 // Internal: nothing here is part of include/rm_api.h.
 #pragma once
@@ -14,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "rm_accum_args.hpp"
 #include "rm_adaptive_args.hpp"
 #include "rm_comm.hpp"
 #include "rm_internal.hpp"
@@ -74,6 +76,11 @@ hipError_t launch_table_adapt_refine(const rmd::Frame& F, const rmd::AdaptArgs& 
 // are pixel_grid's with aa set, at the pattern's device table P
 hipError_t launch_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
 hipError_t launch_table_pattern(const rmd::Frame& F, const rmd::PatternArgs& P, hipStream_t s);
+// an accumulating pattern frame (rm_accum.hip, rm_table_accum.hip): launch_pattern's frame and
+// table, and the sum image, the divisor and whether the sum is continued (rm_accum_args.hpp)
+hipError_t launch_accum(const rmd::Frame& F, const rmd::PatternArgs& P, const rmd::AccumArgs& A, hipStream_t s);
+hipError_t launch_table_accum(const rmd::Frame& F, const rmd::PatternArgs& P, const rmd::AccumArgs& A,
+                              hipStream_t s);
 // pattern refinement in the adaptive calls (rm_adaptive_pattern.hip, rm_table_adaptive_pattern.hip):
 // the listed pixels rendered as the pattern frame's, at the pattern's device table P, on `waves`
 // one-wave workgroups
@@ -121,6 +128,7 @@ struct SceneKernels {
   decltype(launch_adapt_refine)* adapt_refine;
   decltype(launch_pattern)* pattern;
   decltype(launch_adapt_refine_pattern)* adapt_refine_pattern;
+  decltype(launch_accum)* accum;
 };
 
 // A device buffer the context owns and grows on demand (rm_api_query.hip ensure).
@@ -246,6 +254,10 @@ struct rm_ctx {
   float* pat_host = nullptr;     // the table's pinned host copy, the source of the upload
   hipEvent_t pat_ev = nullptr;   // the last upload, on the stream it was queued on
   bool pat_ev_pending = false;   // recorded and not yet waited for: pat_host is still being read
+  // progressive accumulation (rm_api_accum.hip): the sum image [height][width] float4, allocated
+  // on first use, and the samples in it; only rm_dispatch_accumulate and rm_accum_reset touch them
+  float* d_accum = nullptr;
+  int64_t accum_n = 0;
   // a multi-GPU context (rm_config.ngpus): one shard context per device, subs[0] = rank 0
   std::vector<rm_ctx*> subs;
   std::string err;

@@ -340,4 +340,30 @@ int rm_pattern_uv_table(const rm_sample_pattern* p, int32_t width, int32_t heigh
   return RM_OK;
 }
 
+// (include/rm_api.h RM_HAS_ACCUMULATION) The radical inverse in double, every operation
+// one IEEE double operation in the header's order: the product and the sum are separate.
+static double radical_inverse(int64_t i, int b) {
+  double f = 1.0 / b, r = 0.0;
+  while (i > 0) {
+    const double term = (double)(i % b) * f;
+    r = r + term;
+    i = i / b;
+    f = f / (double)b;
+  }
+  return r;
+}
+
+int rm_sample_pattern_halton(rm_sample_pattern* p, int64_t first, int32_t n) {
+  if (!p || n < 1 || n > RM_MAX_SAMPLES || first < 0 || first > ((int64_t)1 << 40)) return RM_ERR_INVALID;
+  std::memset(p, 0, sizeof *p);
+  p->struct_size = (uint32_t)sizeof *p;
+  p->n = n;
+  for (int s = 0; s < n; ++s) {
+    const int64_t i = first + s + 1;
+    p->dx[s] = (float)(radical_inverse(i, 2) - 0.5);
+    p->dy[s] = (float)(radical_inverse(i, 3) - 0.5);
+  }
+  return RM_OK;
+}
+
 }  // extern "C"

@@ -58,6 +58,9 @@ RM_PATTERN_RGSS = 2        # n 4, rotated grid
 RM_PATTERN_GRID3 = 3       # n 9, {-.34375, 0, +.34375}^2, x fastest
 RM_PATTERN_GRID4 = 4       # n 16, {-.375, -.125, +.125, +.375}^2, x fastest
 RM_HAS_ADAPTIVE_PATTERN = 1  # Renderer.dispatch_adaptive_pattern / dispatch_refine_pattern
+# progressive accumulation (rm_dispatch_accumulate)
+RM_HAS_ACCUMULATION = 1  # Renderer.dispatch_accumulate / accumulate
+RM_ACCUM_RESTART = 1     # flags: N = 0 first, the call's samples replace the sum
 RM_SHADOW_SOFT = 0
 RM_SHADOW_HARD = 1
 RM_KERNEL_AUTO = 0
@@ -349,6 +352,12 @@ _SIGS = {
     "rm_dispatch_adaptive_pattern": (C.c_int, [_P, C.POINTER(rm_aa_criteria), C.POINTER(rm_sample_pattern)]),
     "rm_dispatch_refine_pattern": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(rm_sample_pattern)]),
     "rm_dispatch_refine_pattern_device": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(rm_sample_pattern)]),
+    "rm_dispatch_accumulate": (C.c_int, [_P, C.POINTER(rm_sample_pattern), C.c_uint32]),
+    "rm_accum_reset": (C.c_int, [_P]),
+    "rm_accum_samples": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "rm_read_accum": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
+    "rm_get_accum": (C.c_int, [_P, C.POINTER(_P)]),
+    "rm_sample_pattern_halton": (C.c_int, [C.POINTER(rm_sample_pattern), C.c_int64, C.c_int32]),
 }
 COMM_ID_BYTES = 128
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -437,6 +446,15 @@ def pattern_uv_table(p: rm_sample_pattern, width: int, height: int) -> tuple:
     if rc < 0:
         raise RMError(rc, "rm_pattern_uv_table: invalid pattern or frame size")
     return uvx, uvy
+
+
+def halton_pattern(first: int, n: int) -> rm_sample_pattern:
+    """n points of the Halton sequence in bases 2 and 3 from index `first`, re-centred on the
+    pixel (rm_sample_pattern_halton): the patterns Renderer.accumulate walks.  Pure host math."""
+    p = rm_sample_pattern()
+    if lib().rm_sample_pattern_halton(C.byref(p), int(first), int(n)) < 0:
+        raise RMError(RM_ERR_INVALID, "rm_sample_pattern_halton: n must be in 1..RM_MAX_SAMPLES, first in 0..2^40")
+    return p
 
 
 # ---- Camera (source/camera.hpp:12-35) --------------------------------------------------
@@ -767,6 +785,53 @@ class Renderer:
             self.set_uniforms(u)
         p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
         _check(lib().rm_dispatch_pattern(self._h, C.byref(p)), self._h)
+
+    # -- progressive accumulation (rm_dispatch_accumulate)
+    def dispatch_accumulate(self, u: Optional[rm_uniforms] = None, pattern=RM_PATTERN_REFERENCE,
+                            restart: bool = False) -> None:
+        """dispatch_pattern's samples added onto the context's sum image, and the frame the
+        mean of every sample since the sum was last restarted (rm_dispatch_accumulate).
+        `pattern` as in dispatch_pattern; restart: the call's samples replace the sum
+        (RM_ACCUM_RESTART).  Nothing else resets the sum: uniforms changed between calls blend
+        (motion blur, area lights, depth of field).  Asynchronous; reads back like dispatch()."""
+        if u is not None:
+            self.set_uniforms(u)
+        p = pattern if isinstance(pattern, rm_sample_pattern) else sample_pattern(int(pattern))
+        _check(lib().rm_dispatch_accumulate(self._h, C.byref(p), RM_ACCUM_RESTART if restart else 0), self._h)
+
+    def accumulate(self, u: Optional[rm_uniforms], samples: int, first: int = 0) -> None:
+        """`samples` more samples per pixel of u (None: the current uniforms) onto the sum, as
+        Halton patterns of up to RM_MAX_SAMPLES from index `first` (halton_pattern); continue a
+        sequence with first = accum_samples()."""
+        if samples < 1:
+            raise ValueError("accumulate: samples must be at least 1")
+        done = 0
+        while done < samples:
+            n = min(RM_MAX_SAMPLES, samples - done)
+            self.dispatch_accumulate(u if done == 0 else None, halton_pattern(first + done, n))
+            done += n
+
+    def accum_reset(self) -> None:
+        """Forget the sum: the next dispatch_accumulate starts a new one (rm_accum_reset)."""
+        _check(lib().rm_accum_reset(self._h), self._h)
+
+    def accum_samples(self) -> int:
+        """Samples per pixel in the sum (rm_accum_samples)."""
+        n = C.c_int64(0)
+        _check(lib().rm_accum_samples(self._h, C.byref(n)), self._h)
+        return int(n.value)
+
+    def read_accum(self, flip_y: bool = False) -> np.ndarray:
+        """The sum image (rm_read_accum): [height, width, 4] float32, (S.r, S.g, S.b, N)."""
+        out = np.empty((self.rows, self.width, 4), np.float32)
+        _check(lib().rm_read_accum(self._h, out.ctypes.data, 0, int(flip_y)), self._h)
+        return out
+
+    def accum_ptr(self) -> int:
+        """Device address of the sum image (rm_get_accum), allocated on first use."""
+        p = C.c_void_p()
+        _check(lib().rm_get_accum(self._h, C.byref(p)), self._h)
+        return p.value or 0
 
     # -- pattern refinement (rm_dispatch_adaptive_pattern, rm_dispatch_refine_pattern)
     def dispatch_adaptive_pattern(self, u: Optional[rm_uniforms] = None, criteria=None,
